@@ -7,14 +7,24 @@ synthetic BASELINE config 3 workload (n=1024 nodes, latent_dim=16 -> d=34,
 T=128 time steps per GPU; weak scaling T_total = 128 * N, time-sharded).
 Units per step = T_total * n(n-1)/2 (the unordered dyad-timesteps the ELBO sums).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  Inputs are resident in HBM before timing; the
 timed region is K full fit() iterations bracketed by barrier + synchronize,
-max over ranks.  `roofline` is for the dominant kernel, timed with HIP events
-on the stream it runs on; `cpu_baseline` times the numpy oracle
-(oracle/ame_oracle.py) on a bounded sample of the same workload on this host.
+max over ranks.  A plain run does only that: set-up, W warmup iterations, the K
+timed ones, the result line (`value`, `ms_per_step`, the configuration, the
+schedule, the last ELBO / MSE).
+
+`--dump-outputs DIR` writes what the timed fit() left its caller after its last
+iteration as DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
+
+`--full` adds everything that takes runs of its own, after the timed region:
+per-kernel HIP events inside the timed fit(), `kernels` / `roofline` (the
+dominant kernel; covariance terms and ELBO from isolated launches),
+`cpu_baseline` (the numpy oracle, oracle/ame_oracle.py, on this host) and
+`secondary` (BASELINE config 5's per-rank shape on the same GPU).
 """
 import argparse
 import json
@@ -419,6 +429,95 @@ def config5_full(dev, steps=3, warmup=1, variants=("naive", "good", "bad"), opts
     return out
 
 
+def kernel_report(eng, args, n, d, r, ms_step):
+    """--full: every kernel's algorithmic bytes, time and share of the HBM peak
+    (the sweep per iteration; covariance terms and ELBO from isolated launches
+    after the timed region), with the committed PMC traffic for this shape."""
+    kms, _ = eng.kernel_ms()
+    kb = kernel_bytes(n, eng.shard.T_local, d, eng.swap_consistent)
+    tag = f"n{n}_T{args.t_per_gpu}_r{r}_{args.variant}"
+    pmc_all = load_pmc(tag) or {}
+    pmc = pmc_all.get("kernels", {})
+    # cov / elbo launches once more, alone on the GPU (after the timed region)
+    iso = isolated_ms(eng)
+    kernels = {}
+    for name, ms, how in (
+            ("sweep", ms_step, "per-iteration time (one sweep retires per fit() iteration; "
+                               "pipelined launches overlap, so a launch's own duration is not "
+                               "a per-sweep figure)"),
+            ("cov", iso.get("cov"), "isolated launch, HIP events on its stream"),
+            ("elbo", iso.get("elbo"), "isolated launch (pair + node + final kernels), HIP "
+                                      "events on its stream"),
+            ("pairs", iso.get("pairs"), "the ELBO pair kernel alone (ame_pairs2_kernel, MFMA), "
+                                        "isolated launch, HIP events on its stream")):
+        ent = {"alg_bytes": kb[name], "ms": ms, "timing": how,
+               "launch_ms_in_fit": kms.get(name)}
+        if ms:
+            ach = kb[name] / (ms * 1e-3) / 1e9
+            ent.update(achieved_GBs=ach, frac=ach / HBM_PEAK_GBS)
+        if name == "sweep" and kms.get("sweep"):
+            # the same bytes over the launch's own HIP-event duration (the rocprof
+            # kernel-statistics basis): a pipelined launch's span includes waiting
+            # for the previous sweep's slices, so this is the lower of the two
+            ent["frac_per_launch"] = kb[name] / (kms["sweep"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+            ent["frac_basis"] = {"frac": "algorithmic bytes / ms_per_step (one sweep retires "
+                                         "per iteration)",
+                                 "frac_per_launch": "algorithmic bytes / launch_ms_in_fit "
+                                                    "(HIP events around each launch)"}
+        pk = pmc.get({"elbo": "pairs"}.get(name, name))   # elbo: its dominant (pair) kernel
+        if pk:
+            ent["traffic"] = pk.get("hbm_bytes_per_launch")
+            ent["traffic_kernel"] = pk.get("kernel")
+            ent["traffic_source"] = pmc_all.get("_file")
+            if ent["traffic"]:
+                alg = kb[name] if name != "elbo" else pk.get("alg_bytes", kb[name])
+                ent["traffic_over_alg"] = ent["traffic"] / alg
+            if name == "pairs" and pk.get("mfma_busy") is not None:
+                ent["mfma_busy"] = pk["mfma_busy"]
+                ent["mfma_method"] = pk.get("mfma_method")
+        kernels[name] = ent
+    return kernels
+
+
+DUMP_ARRAY_BYTES = 24 << 20   # per state array; everything dumped stays under 64 MB
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(path, vi, hist, steps, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed fit() holds after its last
+    iteration, one float .npy each:
+
+    * elbo, reconstruction_error (float64, K): the history of the K timed steps;
+    * X_mean (float32, (n, T_local, d)) and X_cov (float32): this rank's slices
+      of the fitted state in the reference layout.  An array larger than
+      DUMP_ARRAY_BYTES is reduced to a fixed sample of its (node, slice) rows,
+      row i * T_local + t, drawn without replacement by
+      numpy.random.default_rng(DUMP_SAMPLE_SEED) and sorted (config 3: all of
+      X_mean, 5442 of the 131072 covariances, as (rows, d, d)).
+
+    Ranks above 0 (torchrun) add _rank<k> to the names.  Returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    eng = vi.engine
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arrays = {"elbo": np.asarray([float(e) for e in hist["elbo"][-steps:]], dtype=np.float64),
+              "reconstruction_error": np.asarray([float(e) for e in
+                                                  hist["reconstruction_error"][-steps:]],
+                                                 dtype=np.float64)}
+    for name, t in (("X_mean", eng.means_local()), ("X_cov", eng.covs_local())):
+        n, TL = t.shape[:2]
+        rows = n * TL
+        row_bytes = 4 * int(np.prod(t.shape[2:]))
+        keep = max(1, min(rows, DUMP_ARRAY_BYTES // row_bytes))
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, keep, replace=False))
+            idx = torch.from_numpy(idx).to(t.device)
+            t = t[idx // TL, idx % TL]
+        arrays[name] = t.detach().float().cpu().contiguous().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), a)
+    return {f"{name}{sfx}": list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     # stdout carries exactly one JSON line: anything a library prints there
     # (RCCL's version banner at communicator creation, ...) goes to stderr
@@ -434,11 +533,18 @@ def main():
     ap.add_argument("--latent-dim", type=int, default=16)
     ap.add_argument("--variant", default="good", choices=["good", "bad", "naive"])
     ap.add_argument("--lr", type=float, default=0.01)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also: per-kernel times and roofline (isolated "
+                         "launches), the CPU baselines and the config-5 secondary measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (ELBO / MSE history, fitted means, "
+                         "a fixed sample of the covariances) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines (and the secondary measurement)")
     ap.add_argument("--cpu-budget", type=float, default=40.0)
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the second, untimed-by-the-driver measurement of BASELINE "
-                         "config 5's per-rank shape (N=1 default runs only)")
+                    help="with --full: skip the second, untimed-by-the-driver measurement of "
+                         "BASELINE config 5's per-rank shape (N=1 default-shape runs only)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="sweeps in order (profiling: per-dispatch counters without the "
                          "pipelined launches' waiting)")
@@ -462,6 +568,8 @@ def main():
                     help="BASELINE config 5's own workload (n=4096, T=256, r=32) three-way on "
                          "this one GPU; prints its own JSON line instead of the metric")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -516,7 +624,8 @@ def main():
     if args.warmup > 0:
         vi.fit(max_iter=args.warmup, tolerance=0.0, verbose=False)
     eng = vi.engine
-    eng.timing = True
+    # HIP events around every kernel launch of the timed fit(): --full only
+    eng.timing = bool(args.full)
     eng.events.clear()
 
     def barrier():
@@ -546,69 +655,30 @@ def main():
         tt = tt[:1].clone()
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    kms, kcount = eng.kernel_ms()
-    TL = eng.shard.T_local
-    kb = kernel_bytes(n, TL, d, eng.swap_consistent)
     units_per_step = T_total * n * (n - 1) / 2.0
     value = units_per_step * args.steps / dt
     ms_step = dt / args.steps * 1e3
     b_iter = 8.0 * n * (n - 1) * T_total + 4.0 * n * (n - 1) * T_total \
         + 12.0 * n * T_total * d * d + 16.0 * n * T_total * d
-    tag = f"n{n}_T{args.t_per_gpu}_r{r}_{args.variant}"
-    pmc_all = load_pmc(tag) or {}
-    pmc = pmc_all.get("kernels", {})
-    # cov / elbo launches once more, alone on the GPU (after the timed region)
-    iso = isolated_ms(eng)
     pipelined = bool(getattr(eng, "pipelined", False))
-    kernels = {}
-    for name, ms, how in (
-            ("sweep", ms_step, "per-iteration time (one sweep retires per fit() iteration; "
-                               "pipelined launches overlap, so a launch's own duration is not "
-                               "a per-sweep figure)"),
-            ("cov", iso.get("cov"), "isolated launch, HIP events on its stream"),
-            ("elbo", iso.get("elbo"), "isolated launch (pair + node + final kernels), HIP "
-                                      "events on its stream"),
-            ("pairs", iso.get("pairs"), "the ELBO pair kernel alone (ame_pairs2_kernel, MFMA), "
-                                        "isolated launch, HIP events on its stream")):
-        ent = {"alg_bytes": kb[name], "ms": ms, "timing": how,
-               "launch_ms_in_fit": kms.get(name)}
-        if ms:
-            ach = kb[name] / (ms * 1e-3) / 1e9
-            ent.update(achieved_GBs=ach, frac=ach / HBM_PEAK_GBS)
-        if name == "sweep" and kms.get("sweep"):
-            # the same bytes over the launch's own HIP-event duration (the rocprof
-            # kernel-statistics basis): a pipelined launch's span includes waiting
-            # for the previous sweep's slices, so this is the lower of the two
-            ent["frac_per_launch"] = kb[name] / (kms["sweep"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-            ent["frac_basis"] = {"frac": "algorithmic bytes / ms_per_step (one sweep retires "
-                                         "per iteration)",
-                                 "frac_per_launch": "algorithmic bytes / launch_ms_in_fit "
-                                                    "(HIP events around each launch)"}
-        pk = pmc.get({"elbo": "pairs"}.get(name, name))   # elbo: its dominant (pair) kernel
-        if pk:
-            ent["traffic"] = pk.get("hbm_bytes_per_launch")
-            ent["traffic_kernel"] = pk.get("kernel")
-            ent["traffic_source"] = pmc_all.get("_file")
-            if ent["traffic"]:
-                alg = kb[name] if name != "elbo" else pk.get("alg_bytes", kb[name])
-                ent["traffic_over_alg"] = ent["traffic"] / alg
-            if name == "pairs" and pk.get("mfma_busy") is not None:
-                ent["mfma_busy"] = pk["mfma_busy"]
-                ent["mfma_method"] = pk.get("mfma_method")
-        kernels[name] = ent
-    sw = kernels["sweep"]
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, vi, hist, args.steps, rank, world)
+    # --full: per-kernel figures from the timed fit()'s HIP events and from
+    # launches of their own, after the timed region and the dump
+    kernels = kernel_report(eng, args, n, d, r, ms_step) if args.full else None
 
     out = None
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(model, vi, n, T_total, d, budget_s=args.cpu_budget)
         elbo_last = float(hist["elbo"][-1])
         shape = (n, args.t_per_gpu, r)
         secondary = None
-        # the full default run only (tools pass --no-cpu-baseline: profiler passes
-        # and A/B runs see the config-3 kernels alone)
-        if (world == 1 and not args.no_secondary and not args.no_cpu_baseline
+        # the --full default-shape run only (tools pass --no-cpu-baseline: profiler
+        # passes see the config-3 kernels alone)
+        if (args.full and world == 1 and not args.no_secondary and not args.no_cpu_baseline
                 and shape == (1024, 128, 16) and args.variant == "good"):
             secondary = secondary_config5(dev)
         named = {(1024, 128, 16): "BASELINE config 3 shape per GPU",
@@ -630,15 +700,7 @@ def main():
                 "sweep_kind": int(vi.engine.sweep_kind),
                 **({"elbo_cus": args.elbo_cus} if args.elbo_cus else {}),
             },
-            "roofline": {"bound": "hbm", "kernel": "sweep", "achieved": sw["achieved_GBs"],
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": sw["frac"],
-                         "traffic": sw.get("traffic"),
-                         "note": ("achieved = the sweep's algorithmic bytes per launch "
-                                  "(DESIGN.md §4) / ms_per_step: one sweep retires per "
-                                  "iteration" + ("; launches are pipelined" if pipelined else "")
-                                  + ". The sweep is latency-bound: n dependent node steps "
-                                  "per slice")},
-            "kernels": kernels,
+            "full": bool(args.full),
             "schedule": {"pipelined": pipelined,
                          "sweeps_queued_ahead": int(getattr(eng, "spec_depth", 1)),
                          "elbo_first": bool(getattr(eng, "elbo_first", False))},
@@ -652,11 +714,25 @@ def main():
                                            pipelined),
             "build": _lib_provenance(),
             "iteration_roofline_frac": b_iter / (dt / args.steps) / (world * HBM_PEAK_GBS * 1e9),
-            "cpu_baseline": cpu,
-            "secondary": secondary,
             "elbo_last": elbo_last,
             "mse_last": float(hist["reconstruction_error"][-1]),
+            "outputs_dumped": dumped,
         }
+        if args.full:
+            sw = kernels["sweep"]
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": "sweep", "achieved": sw["achieved_GBs"],
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": sw["frac"],
+                             "traffic": sw.get("traffic"),
+                             "note": ("achieved = the sweep's algorithmic bytes per launch "
+                                      "(DESIGN.md §4) / ms_per_step: one sweep retires per "
+                                      "iteration" + ("; launches are pipelined" if pipelined else "")
+                                      + ". The sweep is latency-bound: n dependent node steps "
+                                      "per slice")},
+                "kernels": kernels,
+                "cpu_baseline": cpu,
+                "secondary": secondary,
+            })
         print(json.dumps(out), file=json_out, flush=True)
     if use_dist:
         dist.barrier()

@@ -11,12 +11,12 @@ if [[ $WHAT == all || $WHAT == tests ]]; then
   tail -3 $OUT/pytest_gpu.log
 fi
 if [[ $WHAT == all || $WHAT == bench ]]; then
-  timeout -k 10 300 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -30 $OUT/bench.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -30 $OUT/bench.err; exit 1; }
   cat $OUT/bench.json
 fi
 if [[ $WHAT == all || $WHAT == prof ]]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-     python3 -u bench.py --no-cpu-baseline --steps 5 --warmup 1 > $OUT/prof_bench.json 2> $OUT/prof.err \
+     python3 -u bench.py --full --no-cpu-baseline --steps 5 --warmup 1 > $OUT/prof_bench.json 2> $OUT/prof.err \
      || { echo "rocprof failed"; tail -30 $OUT/prof.err; exit 1; }
   find $OUT/prof -name '*kernel_stats.csv' | head -3
 fi

@@ -9,7 +9,7 @@ TAG=${1:-configs}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/$TAG; mkdir -p $OUT; : > $OUT/configs.jsonl
 run() {
-  timeout -k 10 300 python3 -u bench.py --no-cpu-baseline "$@" >> $OUT/configs.jsonl 2> $OUT/err.log \
+  timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline "$@" >> $OUT/configs.jsonl 2> $OUT/err.log \
     || { echo "bench $* failed"; tail -20 $OUT/err.log; exit 1; }
   tail -1 $OUT/configs.jsonl | cut -c1-400
 }

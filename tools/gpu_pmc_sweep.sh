@@ -12,7 +12,7 @@ PC="SQC_ICACHE_MISSES SQC_ICACHE_HITS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 for P in A B C; do
   eval CN=\$P$P
   timeout -s KILL 90 rocprofv3 --pmc $CN --kernel-include-regex ame_sweep --output-format csv \
-    -d $OUT/p$P -o pmc -- python3 -u bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" \
+    -d $OUT/p$P -o pmc -- python3 -u bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" \
     > $OUT/p$P.log 2>&1 || { echo "pmc $P failed"; tail -5 $OUT/p$P.log; exit 1; }
 done
 python3 tools/pmc_sq.py $OUT ${N:-1024} ${TL:-128} | tee $OUT/sq.txt

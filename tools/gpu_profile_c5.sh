@@ -7,7 +7,7 @@ set -o pipefail
 TAG=${1:-c5prof}; VAR=${2:-good}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-ARGS="--n 4096 --t-per-gpu 32 --latent-dim 32 --variant $VAR --no-cpu-baseline"
+ARGS="--n 4096 --t-per-gpu 32 --latent-dim 32 --variant $VAR --full --no-cpu-baseline"
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 240 rocprofv3 --pmc $C --kernel-include-regex 'ame_' --output-format csv \
       -d $OUT/pmc_$C -o pmc -- python3 -u bench.py $ARGS --steps 3 --warmup 1 \
