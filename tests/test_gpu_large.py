@@ -33,11 +33,21 @@ def _params(m, dtype=np.float64):
     return {k: getattr(m, k).numpy().astype(dtype) for k in PKEYS}
 
 
-def _check_vs_oracle(n, T, r, method, lr, dev, iters=2, **opts):
+def _check_vs_oracle(n, T, r, method, lr, dev, iters=2, model_hook=None, data_hook=None,
+                     check_terms=False, **opts):
+    """`model_hook(model)` is called with the freshly built model before data
+    generation and may overwrite its six parameter attributes (PKEYS);
+    `data_hook(model)` after it and may edit Y.  Both sides follow: the oracle's
+    `params` and Y are read from the model below.  `check_terms` also holds each
+    of the four ELBO terms of the final state to 5e-6 |ELBO|."""
     import ame_oracle as O
     from ame_amd import TemporalAMEModel
     m = TemporalAMEModel(n, T, r, seed=7)
+    if model_hook is not None:
+        model_hook(m)
     m.generate_data_fast(seed=11)
+    if data_hook is not None:
+        data_hook(m)
     vi = _vi(m, method, lr, dev, **opts)
     Xm = vi.X_mean.numpy().astype(np.float64).copy()
     Xc = vi.X_cov.numpy().astype(np.float64).copy()
@@ -65,6 +75,12 @@ def _check_vs_oracle(n, T, r, method, lr, dev, iters=2, **opts):
         assert abs(float(a) - b) <= 5e-6 * abs(b), (float(a), b)
     for a, b in zip(h["reconstruction_error"], ref["reconstruction_error"]):
         assert abs(a - b) <= 5e-6 * abs(b), (a, b)
+    if check_terms:
+        # a wrong term cannot hide behind a compensating one
+        sp = vi.elbo_terms()
+        got = np.array([sp["loglik"], sp["prior0"], sp["trans"], sp["entropy"]])
+        want = O.elbo_split(m.Y.numpy().astype(np.float64), Xm, Xc, params, method)
+        assert np.all(np.abs(got - want) <= 5e-6 * abs(want.sum())), (got, want)
     return vi
 
 
