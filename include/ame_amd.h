@@ -24,6 +24,11 @@
  *                     compute_temporal_reconstruction_error
  *                     (temporal_ame.py:255-291): returns the sufficient sums
  *                     from which the host assembles ELBO and MSE.
+ *   ame_predict       replaces nothing in the reference: posterior-predictive
+ *                     mean and 2x2 covariance of every dyad from (means,
+ *                     covariances), scored against the observed network
+ *                     (the input metrics.py:350-518 expects and nothing there
+ *                     produces), as per-slice sums or a dense block.
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -280,6 +285,60 @@ long long ame_elbo_work_size(const ame_dims* dims);
  * (its per-workgroup partials land in args->work; args->out is NOT written).
  * Not part of an iteration; bench.py times the pair kernel alone with it. */
 int ame_elbo_pairs_diag(const ame_dims* dims, const ame_elbo_args* args, void* stream);
+
+/* ---- posterior-predictive dyad moments and scoring ---------------------------
+ * Replaces nothing the reference computes: it supplies what its
+ * calibration_error / compute_coverage / temporal_prediction_metrics
+ * (src/utils/metrics.py:350-518) take as input, predictive intervals of the
+ * dyads, from the means AND covariances of q.  With q(x_i) = N(m_i, S_i)
+ * independent across nodes and mu_ij = (a_i + b_j + U_i.V_j, a_j + b_i + U_j.V_i)
+ * (static_ame.py:189-238), for i != j
+ *   E[mu_ij[0]]  = m_i[a] + m_j[b] + u_i.v_j
+ *   V0(i,j)      = Var[mu_ij[0]] = S_i[aa] + S_j[bb] + v_j' S_i[UU] v_j
+ *                  + u_i' S_j[VV] u_i + tr(S_i[UU] S_j[VV]) + 2 S_i[aU].v_j + 2 u_i.S_j[bV]
+ *   Var[mu_ij[1]] = V0(j,i)
+ *   C01(i,j)     = Cov[mu_ij[0], mu_ij[1]] = S_i[ab] + S_j[ab] + u_j.S_i[aV] + S_j[bU].v_i
+ *                  + S_i[bU].v_j + u_i.S_j[aV] + tr(C_i C_j) + v_j' C_i u_j + v_i' C_j u_i,
+ *                  C = S[UV] (rows U, columns V)
+ * and the predictive covariance of (y_ij, y_ji) is [[V0(i,j), C01], [C01, V0(j,i)]] + N
+ * (N = `noise`, symmetric: model.R for observations, zeros for the mean).  Any
+ * variant's covariances are read as full d x d matrices.  The slices are
+ * independent: dims.t_begin / T_total / variant are only range-checked, so a
+ * caller may pass any [S][n][..] stack (forecast states) with T_local = S.
+ *
+ * Scoring (sums != NULL, needs Yt): unordered pairs i < j with the upper
+ * triangle Yt[t][i][j] as the observation (structured_mf.py:136-137),
+ * e = y - E[mu_ij], z_c^2 = e_c^2 / Sigma_cc, m^2 = e' Sigma^-1 e.  Per slice:
+ *   [0] pairs scored   [1] sum log N(y; E[mu], Sigma)   [2] sum m^2
+ *   [3],[4] sum z_0^2, z_1^2   [5],[6] sum Sigma_00, Sigma_11   [7],[8] sum e_0^2, e_1^2
+ *   [9+3l],[10+3l],[11+3l] counts of z_0^2 <= zsq[l], z_1^2 <= zsq[l], m^2 <= csq[l]
+ * (slots of levels >= n_levels are 0).  The sums are per-workgroup fp64
+ * partials reduced in a fixed order: bit-identical from run to run.
+ * Dense (dense != NULL): the five moments of every ordered pair of the block
+ * rows [i0, i1) x columns [j0, j1); on the diagonal i == j the means are
+ * compute_mean's and the three second moments are NaN (the independence the
+ * formulas rest on does not hold there). */
+#define AME_PREDICT_MAX_LEVELS 4
+#define AME_PREDICT_SUMS (9 + 3 * AME_PREDICT_MAX_LEVELS)
+typedef struct ame_predict_args {
+    const float* x;      /* [S][n][d] means              (S = dims.T_local)           */
+    const float* cov;    /* [S][n][d][d] covariances                                  */
+    const float* Yt;     /* [S][n][ny][2] packed observations (ame_pack_y), or NULL:
+                            no scoring, sums not written                              */
+    double noise[4];     /* N, row-major; zeros = moments of the mean                 */
+    int32_t n_levels;    /* 0..AME_PREDICT_MAX_LEVELS                                 */
+    double zsq[AME_PREDICT_MAX_LEVELS];  /* marginal thresholds on z^2                */
+    double csq[AME_PREDICT_MAX_LEVELS];  /* joint thresholds on the Mahalanobis^2     */
+    double* sums;        /* [S][AME_PREDICT_SUMS] fp64, or NULL                       */
+    float* dense;        /* [S][i1-i0][j1-j0][5] = mean0, mean1, var0, var1, cov01
+                            (noise included as given), or NULL                        */
+    int32_t i0, i1, j0, j1;              /* dense block, ignored when dense == NULL   */
+    double* work;        /* >= ame_predict_work_size() doubles                        */
+} ame_predict_args;
+int ame_predict(const ame_dims* dims, const ame_predict_args* args, void* stream);
+/* Scratch doubles ame_predict needs (per-node feature rows and per-workgroup
+ * partials; nothing of size n^2 per slice beyond 21 doubles per 64 x 64 tile). */
+long long ame_predict_work_size(const ame_dims* dims);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

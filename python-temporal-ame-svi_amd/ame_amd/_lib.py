@@ -66,9 +66,20 @@ class ame_elbo_args(ctypes.Structure):
                 ("pairs_kernel", c_int32)]
 
 
+AME_PREDICT_MAX_LEVELS = 4
+AME_PREDICT_SUMS = 9 + 3 * AME_PREDICT_MAX_LEVELS
+
+
+class ame_predict_args(ctypes.Structure):
+    _fields_ = [("x", c_vp), ("cov", c_vp), ("Yt", c_vp), ("noise", ctypes.c_double * 4),
+                ("n_levels", c_int32), ("zsq", ctypes.c_double * AME_PREDICT_MAX_LEVELS),
+                ("csq", ctypes.c_double * AME_PREDICT_MAX_LEVELS), ("sums", c_vp), ("dense", c_vp),
+                ("i0", c_int32), ("i1", c_int32), ("j0", c_int32), ("j1", c_int32), ("work", c_vp)]
+
+
 # every symbol include/ame_amd.h declares (checked by tests/test_capi.py)
 EXPORTS = ("ame_pack_y", "ame_pack_y_size", "ame_sweep", "ame_sweep_kind", "ame_sweep_work_size", "ame_sweep_orders_slices", "ame_sweep_max_slices", "ame_sweep_slice_workgroups", "ame_sweep_lds_bytes", "ame_cov",
-           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_host_register", "ame_host_unregister",
+           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_host_register", "ame_host_unregister",
            "ame_stream_create_cu_range", "ame_stream_destroy",
            "ame_peer_alloc", "ame_peer_free", "ame_peer_open", "ame_peer_close",
            "ame_peer_probe", "ame_peer_read_u64", "ame_peer_clear",
@@ -96,6 +107,10 @@ def _declare(L):
     L.ame_debug_gw_tag.restype = ctypes.c_uint
     L.ame_elbo_work_size.argtypes = [P(ame_dims)]
     L.ame_elbo_work_size.restype = ctypes.c_longlong
+    L.ame_predict.argtypes = [P(ame_dims), P(ame_predict_args), c_vp]
+    L.ame_predict.restype = ctypes.c_int
+    L.ame_predict_work_size.argtypes = [P(ame_dims)]
+    L.ame_predict_work_size.restype = ctypes.c_longlong
     L.ame_debug_selftest.argtypes = [c_vp, c_vp]
     L.ame_debug_selftest.restype = ctypes.c_int
     if hasattr(L, "ame_debug_occupy"):   # diagnostic; absent from older A/B builds

@@ -16,12 +16,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libame_amd.so")
 SOURCES = ("ame_sweep.hip", "ame_sweep3.hip", "ame_cov.hip", "ame_elbo.hip", "ame_capi.hip",
-           "ame_selftest.hip", "ame_align.hip", "ame_parts.hip")
+           "ame_selftest.hip", "ame_align.hip", "ame_predict.hip", "ame_parts.hip")
 # one-latent-dim diagnostic builds (-DAME_ONLY_R, tools/): no split parts, no router
 UNSPLIT_SOURCES = tuple(s for s in SOURCES if s != "ame_parts.hip")
 # Every latent dim 1..32 is compiled in; the heaviest sources are split into
 # parts by r % parts (ame_common.h AME_R_PART) so the build runs in parallel.
-SPLIT = {"ame_sweep.hip": 3, "ame_sweep3.hip": 2, "ame_elbo.hip": 2}
+SPLIT = {"ame_sweep.hip": 3, "ame_sweep3.hip": 2, "ame_elbo.hip": 2, "ame_predict.hip": 3}
 
 
 def _units():
@@ -129,7 +129,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs = min(len(units), max(1, min(16, os.cpu_count() or 1)))
     # longest units first, so the tail of the parallel build is short
     order = sorted(units, key=lambda u: -{"ame_sweep.hip": 5, "ame_elbo.hip": 4, "ame_align.hip": 3,
-                                          "ame_sweep3.hip": 2}.get(u[0], 1))
+                                          "ame_sweep3.hip": 2, "ame_predict.hip": 2}.get(u[0], 1))
     with cf.ThreadPoolExecutor(jobs) as ex:
         list(ex.map(compile_one, order))
     tmp = OUT + ".tmp"

@@ -22,6 +22,9 @@ int ame_align_cross_dispatch(const float*, const float*, int, int, int, int, dou
 int ame_align_apply_dispatch(const float*, const float*, int, int, int, int, const double*, float*,
                              double*, hipStream_t);
 long long ame_align_partials_count(int n, int T);
+int ame_predict_dispatch(const ame_dims*, const ame_predict_args*, hipStream_t);
+long long ame_predict_work_doubles(const ame_dims*);
+long long ame_predict_max_blocks(const ame_dims*, const ame_predict_args*);
 int ame_pack_dispatch(const float*, float*, const ame_dims*, unsigned long long*, hipStream_t);
 
 static thread_local char g_err[512] = "";
@@ -420,6 +423,29 @@ int ame_elbo_pairs_diag(const ame_dims* dims, const ame_elbo_args* a, void* stre
     if (a->pairs_kernel < AME_PAIRS_AUTO || a->pairs_kernel > AME_PAIRS_V2)
         return fail("ame_elbo_pairs_diag: bad pairs_kernel %d", a->pairs_kernel);
     return launched(ame_elbo_dispatch(dims, a, (hipStream_t)stream, 1), "elbo_pairs");
+}
+
+long long ame_predict_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_predict_work_doubles(dims);
+}
+
+int ame_predict(const ame_dims* dims, const ame_predict_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a || !a->x || !a->cov || !a->work) return fail("ame_predict: NULL buffer (x, cov, work)");
+    if (a->n_levels < 0 || a->n_levels > AME_PREDICT_MAX_LEVELS)
+        return fail("ame_predict: n_levels=%d outside [0, %d]", a->n_levels, AME_PREDICT_MAX_LEVELS);
+    if (a->sums && !a->Yt) return fail("ame_predict: sums need the observations Yt (NULL)");
+    if (a->dense) {
+        if (a->i0 < 0 || a->i0 >= a->i1 || a->i1 > dims->n)
+            return fail("ame_predict: dense rows [%d, %d) outside [0, n]", a->i0, a->i1);
+        if (a->j0 < 0 || a->j0 >= a->j1 || a->j1 > dims->n)
+            return fail("ame_predict: dense columns [%d, %d) outside [0, n]", a->j0, a->j1);
+    }
+    if (ame_predict_max_blocks(dims, a) > 0x7FFFFFFFLL)
+        return fail("ame_predict: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_predict_dispatch(dims, a, (hipStream_t)stream), "predict");
 }
 
 static int check_align(int n, int T, int r) {

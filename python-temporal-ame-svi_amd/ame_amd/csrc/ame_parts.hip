@@ -1,12 +1,13 @@
 // Routes the r-dependent entry points of the split build (build.py compiles
-// ame_sweep.hip in 3 parts, ame_sweep3.hip and ame_elbo.hip in 2; part p holds
+// ame_sweep.hip and ame_predict.hip in 3 parts, ame_sweep3.hip and ame_elbo.hip in 2; part p holds
 // the latent dims r with r % parts == p, ame_common.h) to the part that holds r.
 #include "ame_common.h"
 
 #define AME_DECL_SWEEP(P)                                                                 \
     int ame_sweep_dispatch_p##P(const ame_dims*, const ame_sweep_args*, hipStream_t);     \
     int ame_sweep_blocks_per_cu_p##P(int, int, int);                                      \
-    int ame_sweep_workers_fit_p##P(const ame_dims*, int);
+    int ame_sweep_workers_fit_p##P(const ame_dims*, int);                                 \
+    int ame_predict_dispatch_p##P(const ame_dims*, const ame_predict_args*, hipStream_t);
 AME_DECL_SWEEP(0)
 AME_DECL_SWEEP(1)
 AME_DECL_SWEEP(2)
@@ -55,4 +56,11 @@ int ame_sweep3_lds(int n, int r) {
 int ame_elbo_dispatch(const ame_dims* dm, const ame_elbo_args* a, hipStream_t st, int pairs_only) {
     return (dm->r & 1) ? ame_elbo_dispatch_p1(dm, a, st, pairs_only)
                        : ame_elbo_dispatch_p0(dm, a, st, pairs_only);
+}
+int ame_predict_dispatch(const ame_dims* dm, const ame_predict_args* a, hipStream_t st) {
+    switch (dm->r % 3) {
+        case 0: return ame_predict_dispatch_p0(dm, a, st);
+        case 1: return ame_predict_dispatch_p1(dm, a, st);
+        default: return ame_predict_dispatch_p2(dm, a, st);
+    }
 }

@@ -1,0 +1,428 @@
+// Posterior-predictive dyad moments and scoring (ame_predict, include/ame_amd.h).
+//
+// Every term of V0(i,j), V0(j,i), C01(i,j) and of the two means is an inner
+// product of a per-node feature of i with a per-node feature of j, so a 64 x 64
+// tile of dyads is five small GEMMs over node-feature rows:
+//
+//   segment  length            i-side row . j-side row
+//   Ma, Mb   r + 2             Ma_i.Mb_j = E[mu_ij[0]],  Mb_i.Ma_j = E[mu_ij[1]]
+//   F, G     2 + 2P + 2r       F_i.G_j = V0(i,j),        G_i.F_j = V0(j,i)     P = r(r+1)/2
+//   Pc, Qc   2 + 4r + 2r^2     Pc_i.Qc_j = C01(i,j)
+//
+//   Ma = [a, 1, u]                       Mb = [1, b, v]
+//   F  = [S_aa, 1, pk(S_UU), pk(u u'), 2 S_aU, u]
+//   G  = [1, S_bb, sy(S_VV + v v'), sy(S_VV), v, 2 S_bV]
+//   Pc = [S_ab, 1, S_aV, v, S_bU, u, C, u v']          C = S_UV (rows U, columns V)
+//   Qc = [1, S_ab, u, S_bU, v, S_aV, C' + v u', C']
+// pk() packs a symmetric r x r block to its upper triangle with the two
+// off-diagonal entries added, sy() with their mean, so pk(A).sy(B) = <A, B>.
+// Each segment is zero-padded to a multiple of 4 (the K of v_mfma_f32_16x16x4_f32).
+//
+// K1 ame_predict_feat_kernel: one workgroup per (slice, node) writes the six
+//    segments once (row of PredictCfg<R>::L floats) into `work`.
+// K2 ame_predict_pairs_kernel: one workgroup per (slice, 64 x 64 tile); the
+//    five products stream K in chunks of 32 through LDS (both 64-row operand
+//    tiles, next chunk prefetched into registers during the MFMAs), each wave
+//    keeps its 16 x 64 part of the five results in registers (20 accumulators
+//    of 4) and runs the epilogue on them: scoring in fp64 against Y, read once
+//    from the upper triangle (MODE 0, tiles I <= J), or the dense block (MODE 1).
+// K3 ame_predict_final_kernel: fixed-order sum of a slice's tile partials.
+// No atomics, no spin, no O(n^2) intermediate.
+#include <type_traits>
+
+#include "ame_common.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+#define AME_PT 64        // dyad tile edge
+#define AME_PKB 32       // K chunk in floats
+#define AME_PLD 34       // LDS row stride: 2 li + lq hits 32 distinct banks per half wave
+#define AME_PNS AME_PREDICT_SUMS
+
+__host__ __device__ constexpr int ame_pad4(int k) { return (k + 3) & ~3; }
+// floats of one node's feature row for latent dim r
+__host__ __device__ constexpr int ame_predict_row(int r) {
+    return 2 * ame_pad4(r + 2) + 2 * ame_pad4(2 + r * (r + 1) + 2 * r) + 2 * ame_pad4(2 + 4 * r + 2 * r * r);
+}
+
+template <int R>
+struct PredictCfg {
+    static constexpr int D = 2 + 2 * R, P = R * (R + 1) / 2;
+    static constexpr int KM = R + 2, MP = ame_pad4(KM);
+    static constexpr int KV = 2 + 2 * P + 2 * R, KVP = ame_pad4(KV);
+    static constexpr int KC = 2 + 4 * R + 2 * R * R, KCP = ame_pad4(KC);
+    static constexpr int oMa = 0, oMb = MP, oF = 2 * MP, oG = oF + KVP, oP = oG + KVP, oQ = oP + KCP;
+    static constexpr int L = oQ + KCP;
+    static_assert(L == ame_predict_row(R), "feature row length");
+};
+
+struct PredictParams {
+    int n, S, ny, ntile, ntj, n_levels;
+    int i0, i1, j0, j1;
+    const float* feat;
+    const float* Yt;
+    double n00, n01, n11;
+    double zsq[AME_PREDICT_MAX_LEVELS], csq[AME_PREDICT_MAX_LEVELS];
+    double* partial;   // [S][ntile][AME_PNS]
+    float* dense;
+};
+
+// ---------------------------------------------------------------------------
+// K1: feature rows
+// ---------------------------------------------------------------------------
+template <int R>
+__global__ void __launch_bounds__(AME_NT)
+ame_predict_feat_kernel(const float* __restrict__ x, const float* __restrict__ cov, float* __restrict__ feat) {
+    using C = PredictCfg<R>;
+    constexpr int D = C::D, P = C::P, iU = 2, iV = 2 + R;
+    __shared__ float sc[D * D];
+    __shared__ float sm[D];
+    const size_t node = blockIdx.x;   // slice * n + i
+    const float* cv = cov + node * (size_t)(D * D);
+    for (int e = threadIdx.x; e < D * D; e += AME_NT) sc[e] = cv[e];
+    if (threadIdx.x < D) sm[threadIdx.x] = x[node * D + threadIdx.x];
+    __syncthreads();
+    float* f = feat + node * (size_t)C::L;
+    float* Ma = f + C::oMa;
+    float* Mb = f + C::oMb;
+    float* F = f + C::oF;
+    float* G = f + C::oG;
+    float* Pc = f + C::oP;
+    float* Qc = f + C::oQ;
+    auto Sg = [&](int a, int b) { return sc[a * D + b]; };
+    const int t = threadIdx.x;
+    if (t == 0) {
+        Ma[0] = sm[0]; Ma[1] = 1.f;
+        Mb[0] = 1.f;   Mb[1] = sm[1];
+        F[0] = Sg(0, 0); F[1] = 1.f;
+        G[0] = 1.f;      G[1] = Sg(1, 1);
+        const float sab = 0.5f * (Sg(0, 1) + Sg(1, 0));
+        Pc[0] = sab; Pc[1] = 1.f;
+        Qc[0] = 1.f; Qc[1] = sab;
+        for (int k = C::KM; k < C::MP; ++k) Ma[k] = Mb[k] = 0.f;
+        for (int k = C::KV; k < C::KVP; ++k) F[k] = G[k] = 0.f;
+        for (int k = C::KC; k < C::KCP; ++k) Pc[k] = Qc[k] = 0.f;
+    }
+    if (t < R) {
+        const int k = t;
+        const float u = sm[iU + k], v = sm[iV + k];
+        const float saU = Sg(0, iU + k), saV = Sg(0, iV + k), sbU = Sg(1, iU + k), sbV = Sg(1, iV + k);
+        Ma[2 + k] = u;
+        Mb[2 + k] = v;
+        F[2 + 2 * P + k] = 2.f * saU;
+        F[2 + 2 * P + R + k] = u;
+        G[2 + 2 * P + k] = v;
+        G[2 + 2 * P + R + k] = 2.f * sbV;
+        Pc[2 + k] = saV;
+        Pc[2 + R + k] = v;
+        Pc[2 + 2 * R + k] = sbU;
+        Pc[2 + 3 * R + k] = u;
+        Qc[2 + k] = u;
+        Qc[2 + R + k] = sbU;
+        Qc[2 + 2 * R + k] = v;
+        Qc[2 + 3 * R + k] = saV;
+    }
+    for (int e = t; e < R * R; e += AME_NT) {
+        const int a = e / R, b = e - a * R;
+        const float ua = sm[iU + a], ub = sm[iU + b], va = sm[iV + a], vb = sm[iV + b];
+        const float cba = Sg(iU + b, iV + a);          // C[b][a]
+        Pc[2 + 4 * R + e] = Sg(iU + a, iV + b);        // C[a][b]
+        Pc[2 + 4 * R + R * R + e] = ua * vb;
+        Qc[2 + 4 * R + e] = cba + va * ub;
+        Qc[2 + 4 * R + R * R + e] = cba;
+        if (a <= b) {
+            const int pos = a * R - (a * (a - 1)) / 2 + (b - a);
+            const float w = (a == b) ? 1.f : 2.f;
+            const float suu = (a == b) ? Sg(iU + a, iU + a) : Sg(iU + a, iU + b) + Sg(iU + b, iU + a);
+            const float svv = (a == b) ? Sg(iV + a, iV + a) : 0.5f * (Sg(iV + a, iV + b) + Sg(iV + b, iV + a));
+            F[2 + pos] = suu;
+            F[2 + P + pos] = w * ua * ub;
+            G[2 + pos] = svv + va * vb;
+            G[2 + P + pos] = svv;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// K2: tiled pair kernel
+// ---------------------------------------------------------------------------
+template <int R, int MODE>
+__global__ void __launch_bounds__(AME_NT, 2)
+ame_predict_pairs_kernel(PredictParams p) {
+    using C = PredictCfg<R>;
+    constexpr int L = C::L;
+    const int n = p.n, ntile = p.ntile;
+    const int bb = blockIdx.x;
+    int tl, tile;
+    if ((p.S & 7) == 0) {   // blocks that share an XCD share slices (as ame_pairs2_kernel)
+        const int k = bb >> 3, q = k / ntile;
+        tl = (bb & 7) * (p.S >> 3) + q;
+        tile = k - q * ntile;
+    } else {
+        tl = bb / ntile;
+        tile = bb - tl * ntile;
+    }
+    int I0, J0, ilim, jlim;
+    if (MODE == 0) {   // upper-triangle tiles, row-major: (0,0) (0,1) .. (1,1) ..
+        const int nb = (n + AME_PT - 1) / AME_PT;
+        int I = 0, rem = tile;
+        while (rem >= nb - I) { rem -= nb - I; ++I; }
+        I0 = I * AME_PT;
+        J0 = (I + rem) * AME_PT;
+        ilim = jlim = n;
+    } else {
+        const int ti = tile / p.ntj, tj = tile - ti * p.ntj;
+        I0 = p.i0 + ti * AME_PT;
+        J0 = p.j0 + tj * AME_PT;
+        ilim = p.i1;
+        jlim = p.j1;
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int li = lane & 15, lq = lane >> 4;
+
+    __shared__ __attribute__((aligned(16))) float Il[AME_PT * AME_PLD], Jl[AME_PT * AME_PLD];
+    __shared__ double red[4 * AME_PNS];
+
+    const float* fs = p.feat + (size_t)tl * n * L;
+    // the two float4 of each operand tile this thread stages per chunk
+    const int row0 = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;   // rows row0, row0 + 32
+    const float* gi[2];
+    const float* gj[2];
+    bool oki[2], okj[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int ri = I0 + row0 + 32 * h, rj = J0 + row0 + 32 * h;
+        oki[h] = ri < ilim;
+        okj[h] = rj < jlim;
+        gi[h] = fs + (size_t)(oki[h] ? ri : 0) * L + c4;
+        gj[h] = fs + (size_t)(okj[h] ? rj : 0) * L + c4;
+    }
+
+    f32x4 acc[5][4];
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc[q][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    auto product = [&](auto pidx, int segI, int segJ, int len) {
+        constexpr int PI = decltype(pidx)::value;
+        const int nch = (len + AME_PKB - 1) / AME_PKB;
+        float4 ri[2], rj[2];
+        auto gload = [&](int c) {
+            const int k0 = c * AME_PKB;
+            const bool in = k0 + c4 < len;   // len is a multiple of 4: a float4 is in or out
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                ri[h] = (oki[h] && in) ? *(const float4*)(gi[h] + segI + k0) : z;
+                rj[h] = (okj[h] && in) ? *(const float4*)(gj[h] + segJ + k0) : z;
+            }
+        };
+        gload(0);
+        for (int c = 0; c < nch; ++c) {
+            __syncthreads();   // the previous chunk's fragments have been read
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                float* di = &Il[(row0 + 32 * h) * AME_PLD + c4];
+                float* dj = &Jl[(row0 + 32 * h) * AME_PLD + c4];
+                *(float2*)di = make_float2(ri[h].x, ri[h].y);
+                *(float2*)(di + 2) = make_float2(ri[h].z, ri[h].w);
+                *(float2*)dj = make_float2(rj[h].x, rj[h].y);
+                *(float2*)(dj + 2) = make_float2(rj[h].z, rj[h].w);
+            }
+            __syncthreads();
+            if (c + 1 < nch) gload(c + 1);
+            const int left = (len - c * AME_PKB) >> 2;
+            const int ks = left < AME_PKB / 4 ? left : AME_PKB / 4;
+            const float* ia = &Il[(16 * w + li) * AME_PLD + lq];
+            const float* jb = &Jl[li * AME_PLD + lq];
+#pragma unroll 2
+            for (int kk = 0; kk < ks; ++kk) {
+                const float a = ia[4 * kk];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const float b = jb[16 * s * AME_PLD + 4 * kk];
+                    acc[PI][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[PI][s], 0, 0, 0);
+                }
+            }
+        }
+    };
+    product(std::integral_constant<int, 0>{}, C::oMa, C::oMb, C::MP);
+    product(std::integral_constant<int, 1>{}, C::oMb, C::oMa, C::MP);
+    product(std::integral_constant<int, 2>{}, C::oF, C::oG, C::KVP);
+    product(std::integral_constant<int, 3>{}, C::oG, C::oF, C::KVP);
+    product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
+
+    // accumulator element (s, g) of this lane: i = I0 + 16 w + 4 lq + g, j = J0 + 16 s + li
+    if (MODE == 0) {
+        double sm[AME_PNS];
+#pragma unroll
+        for (int q = 0; q < AME_PNS; ++q) sm[q] = 0.0;
+        const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
+        constexpr double LOG2PI2 = 2.0 * 1.8378770664093454835606594728112;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = J0 + 16 * s + li;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = I0 + 16 * w + 4 * lq + g;
+                if (i < n && j < n && i < j) {
+                    const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
+                    const double e0 = (double)y.x - (double)acc[0][s][g];
+                    const double e1 = (double)y.y - (double)acc[1][s][g];
+                    const double v0 = (double)acc[2][s][g] + p.n00, v1 = (double)acc[3][s][g] + p.n11;
+                    const double c = (double)acc[4][s][g] + p.n01;
+                    const double det = v0 * v1 - c * c;
+                    const double q0 = e0 * e0, q1 = e1 * e1;
+                    const double m2 = (v1 * q0 - 2.0 * c * e0 * e1 + v0 * q1) / det;
+                    const double z0 = q0 / v0, z1 = q1 / v1;
+                    sm[0] += 1.0;
+                    sm[1] += -0.5 * (log(det) + m2 + LOG2PI2);
+                    sm[2] += m2;
+                    sm[3] += z0;
+                    sm[4] += z1;
+                    sm[5] += v0;
+                    sm[6] += v1;
+                    sm[7] += q0;
+                    sm[8] += q1;
+#pragma unroll
+                    for (int l = 0; l < AME_PREDICT_MAX_LEVELS; ++l) {
+                        if (l < p.n_levels) {
+                            sm[9 + 3 * l] += (z0 <= p.zsq[l]) ? 1.0 : 0.0;
+                            sm[10 + 3 * l] += (z1 <= p.zsq[l]) ? 1.0 : 0.0;
+                            sm[11 + 3 * l] += (m2 <= p.csq[l]) ? 1.0 : 0.0;
+                        }
+                    }
+                }
+            }
+        }
+        block_sum<AME_PNS>(sm, red);
+        if (threadIdx.x == 0) {
+            double* o = p.partial + ((size_t)tl * ntile + tile) * AME_PNS;
+#pragma unroll
+            for (int q = 0; q < AME_PNS; ++q) o[q] = sm[q];
+        }
+    } else {
+        const int ni = p.i1 - p.i0, nj = p.j1 - p.j0;
+        const float n00 = (float)p.n00, n01 = (float)p.n01, n11 = (float)p.n11;
+        const float qnan = __builtin_nanf("");
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = J0 + 16 * s + li;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = I0 + 16 * w + 4 * lq + g;
+                if (i < ilim && j < jlim) {
+                    float* o = p.dense + (((size_t)tl * ni + (i - p.i0)) * nj + (j - p.j0)) * 5;
+                    const bool dg = i == j;
+                    o[0] = acc[0][s][g];
+                    o[1] = acc[1][s][g];
+                    o[2] = dg ? qnan : acc[2][s][g] + n00;
+                    o[3] = dg ? qnan : acc[3][s][g] + n11;
+                    o[4] = dg ? qnan : acc[4][s][g] + n01;
+                }
+            }
+        }
+    }
+}
+
+// K3: one workgroup per slice sums its tiles' partials in a fixed order
+static __global__ void __launch_bounds__(AME_NT)
+ame_predict_final_kernel(const double* __restrict__ partial, int ntile, double* __restrict__ sums) {
+    __shared__ double red[4 * AME_PNS];
+    const double* ps = partial + (size_t)blockIdx.x * ntile * AME_PNS;
+    double v[AME_PNS];
+#pragma unroll
+    for (int q = 0; q < AME_PNS; ++q) v[q] = 0.0;
+    for (int b = threadIdx.x; b < ntile; b += AME_NT) {
+#pragma unroll
+        for (int q = 0; q < AME_PNS; ++q) v[q] += ps[(size_t)b * AME_PNS + q];
+    }
+    block_sum<AME_PNS>(v, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < AME_PNS; ++q) sums[(size_t)blockIdx.x * AME_PNS + q] = v[q];
+    }
+}
+
+static inline long long predict_tri_tiles(int n) {
+    const long long nb = (n + AME_PT - 1) / AME_PT;
+    return nb * (nb + 1) / 2;
+}
+static inline long long predict_feat_doubles(const ame_dims* dm) {
+    return ((long long)dm->T_local * dm->n * ame_predict_row(dm->r) + 1) / 2;
+}
+
+#if AME_PART0
+long long ame_predict_work_doubles(const ame_dims* dm) {
+    return predict_feat_doubles(dm) + (long long)dm->T_local * predict_tri_tiles(dm->n) * AME_PNS;
+}
+
+// workgroups of the largest launch ame_predict would make (the caller checks it fits a grid)
+long long ame_predict_max_blocks(const ame_dims* dm, const ame_predict_args* a) {
+    long long m = (long long)dm->T_local * dm->n;
+    if (a->sums) {
+        const long long b = (long long)dm->T_local * predict_tri_tiles(dm->n);
+        m = b > m ? b : m;
+    }
+    if (a->dense) {
+        const long long b = (long long)dm->T_local * ((a->i1 - a->i0 + AME_PT - 1) / AME_PT) *
+                            ((a->j1 - a->j0 + AME_PT - 1) / AME_PT);
+        m = b > m ? b : m;
+    }
+    return m;
+}
+#endif
+
+template <int R>
+static int launch_predict(const ame_dims* dm, const ame_predict_args* a, hipStream_t st) {
+    const int S = dm->T_local, n = dm->n;
+    float* feat = (float*)a->work;
+    hipLaunchKernelGGL(ame_predict_feat_kernel<R>, dim3((unsigned)((long long)S * n)), dim3(AME_NT), 0, st,
+                       a->x, a->cov, feat);
+    PredictParams p;
+    p.n = n;
+    p.S = S;
+    p.ny = ame_ystride(n);
+    p.n_levels = a->n_levels;
+    p.i0 = p.i1 = p.j0 = p.j1 = 0;
+    p.ntj = 1;
+    p.feat = feat;
+    p.Yt = a->Yt;
+    p.n00 = a->noise[0];
+    p.n01 = 0.5 * (a->noise[1] + a->noise[2]);
+    p.n11 = a->noise[3];
+    for (int l = 0; l < AME_PREDICT_MAX_LEVELS; ++l) {
+        p.zsq[l] = l < a->n_levels ? a->zsq[l] : 0.0;
+        p.csq[l] = l < a->n_levels ? a->csq[l] : 0.0;
+    }
+    p.partial = a->work + predict_feat_doubles(dm);
+    p.dense = nullptr;
+    if (a->sums) {
+        p.ntile = (int)predict_tri_tiles(n);
+        hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 0>), dim3((unsigned)((long long)S * p.ntile)),
+                           dim3(AME_NT), 0, st, p);
+        hipLaunchKernelGGL(ame_predict_final_kernel, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
+                           p.ntile, a->sums);
+    }
+    if (a->dense) {
+        p.i0 = a->i0; p.i1 = a->i1; p.j0 = a->j0; p.j1 = a->j1;
+        const int nti = (a->i1 - a->i0 + AME_PT - 1) / AME_PT;
+        p.ntj = (a->j1 - a->j0 + AME_PT - 1) / AME_PT;
+        p.ntile = nti * p.ntj;
+        p.dense = a->dense;
+        hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 1>), dim3((unsigned)((long long)S * p.ntile)),
+                           dim3(AME_NT), 0, st, p);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int AME_PFN(ame_predict_dispatch)(const ame_dims* dm, const ame_predict_args* a, hipStream_t st) {
+    switch (dm->r) {
+#define X(RR) \
+    case RR: return launch_predict<RR>(dm, a, st);
+        AME_FOR_EACH_R(X)
+#undef X
+        default: return -1;
+    }
+}

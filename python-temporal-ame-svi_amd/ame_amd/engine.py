@@ -221,6 +221,7 @@ class Constants:
         self.QiPhi = self.Qinv @ Phi
         self.PhiTQi = Phi.T @ self.Qinv
         self.Phi = Phi
+        self.Q = Q
         self.logdetR = float(torch.logdet(self.R))
         self.trRinv = float(torch.trace(self.R_inv))
         self.logdetS0 = float(torch.logdet(S0))
@@ -807,3 +808,99 @@ class DeviceEngine:
         self.cov.copy_(X_cov[:, t0:t1].detach().float().permute(1, 0, 2, 3))
         self._mark_host_writes()
         self.invalidate()
+
+    # ------------------------------------------------------------------
+    # posterior-predictive dyad moments (ame_predict, include/ame_amd.h)
+    # ------------------------------------------------------------------
+    # scratch budget of one ame_predict call in doubles (256 MiB): longer slice
+    # stacks are scored in chunks of whole slices, which changes no result (the
+    # slices are independent and each keeps its own row of sums)
+    PREDICT_WORK_DOUBLES = 1 << 25
+
+    def noise4(self, include_noise: bool):
+        """N of the predictive covariance: model.R (observations) or zeros (the mean)."""
+        vals = self.C.R.flatten().tolist() if include_noise else [0.0] * 4
+        return (ctypes.c_double * 4)(*vals)
+
+    def pack_future(self, Y_future: torch.Tensor) -> torch.Tensor:
+        """(n, n, h, 2) observations -> the packed [h][n][ny][2] layout (ame_pack_y)."""
+        if Y_future.dim() != 4 or tuple(Y_future.shape[:2]) != (self.n, self.n) \
+                or Y_future.shape[3] != 2 or Y_future.shape[2] < 1:
+            raise ValueError(f"Y_future has shape {tuple(Y_future.shape)}, expected "
+                             f"({self.n}, {self.n}, h, 2)")
+        h = int(Y_future.shape[2])
+        src = Y_future.detach().float().to(self.dev).contiguous()
+        dims = _lib.ame_dims(self.n, self.r, h, 0, h, self.vcode)
+        Yt = torch.empty(h, self.n, self.ny, 2, dtype=torch.float32, device=self.dev)
+        mm = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        _lib.check(self.L.ame_pack_y(_ptr(src), _ptr(Yt), ctypes.byref(dims), _ptr(mm), self._sp()),
+                   "ame_pack_y")
+        return Yt
+
+    def predict(self, x, cov, Yt=None, include_noise=True, zsq=(), csq=(), block=None):
+        """ame_predict over a stack of slices: x [S][n][d], cov [S][n][d][d]
+        (device, fp32, contiguous).  Yt [S][n][ny][2] -> per-slice sums
+        [S][AME_PREDICT_SUMS] (fp64, device); block = (i0, i1, j0, j1) -> dense
+        [S][i1-i0][j1-j0][5] (fp32, device).  Returns (sums or None, dense or
+        None).  Runs on the ELBO stream; the caller has dropped speculation."""
+        S = int(x.shape[0])
+        n, d = self.n, self.d
+        assert tuple(x.shape) == (S, n, d) and tuple(cov.shape) == (S, n, d, d)
+        assert x.is_contiguous() and cov.is_contiguous()
+        nl = len(zsq)
+        one = _lib.ame_dims(n, self.r, 1, 0, 1, self.vcode)
+        per = int(self.L.ame_predict_work_size(ctypes.byref(one)))
+        if per < 0:
+            _lib.check(-1, "ame_predict_work_size")
+        chunk = max(1, min(S, self.PREDICT_WORK_DOUBLES // per))
+        dims = _lib.ame_dims(n, self.r, chunk, 0, chunk, self.vcode)
+        need = int(self.L.ame_predict_work_size(ctypes.byref(dims)))
+        with torch.cuda.device(self.dev):
+            wk = getattr(self, "_predict_work", None)
+            if wk is None or wk.numel() < need:
+                wk = self._predict_work = torch.empty(need, dtype=torch.float64, device=self.dev)
+            sums = torch.zeros(S, _lib.AME_PREDICT_SUMS, dtype=torch.float64,
+                               device=self.dev) if Yt is not None else None
+            dense = None
+            if block is not None:
+                i0, i1, j0, j1 = (int(v) for v in block)
+                dense = torch.empty(S, i1 - i0, j1 - j0, 5, dtype=torch.float32, device=self.dev)
+        st = self._elbo_stream_begin()
+        sp = ctypes.c_void_p(st.cuda_stream)
+        tok = self._tic("predict", st)
+        for s0 in range(0, S, chunk):
+            s1 = min(S, s0 + chunk)
+            dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+            a = _lib.ame_predict_args(
+                x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]), Yt=_ptr(Yt[s0:s1]) if Yt is not None else None,
+                noise=self.noise4(include_noise), n_levels=nl,
+                zsq=(ctypes.c_double * _lib.AME_PREDICT_MAX_LEVELS)(*zsq),
+                csq=(ctypes.c_double * _lib.AME_PREDICT_MAX_LEVELS)(*csq),
+                sums=_ptr(sums[s0:s1]) if sums is not None else None,
+                dense=_ptr(dense[s0:s1]) if dense is not None else None,
+                work=_ptr(wk))
+            if block is not None:
+                a.i0, a.i1, a.j0, a.j1 = i0, i1, j0, j1
+            _lib.check(self.L.ame_predict(ctypes.byref(dm), ctypes.byref(a), sp), "ame_predict")
+        self._toc(tok)
+        self._elbo_stream_end(st)
+        return sums, dense
+
+    def forecast_states(self, m_last: torch.Tensor, S_last: torch.Tensor, n_steps: int):
+        """h-step forecast of the states from the last fitted slice: m_k = Phi
+        m_{k-1}, S_k = Phi S_{k-1} Phi' + Q, batched over nodes in fp64 on the
+        device and rounded to fp32 once.  Returns [h][n][d], [h][n][d][d]."""
+        h = int(n_steps)
+        if h < 1:
+            raise ValueError("n_steps must be >= 1")
+        Phi = self.C.Phi.to(self.dev)
+        Q = self.C.Q.to(self.dev)
+        m = m_last.to(self.dev).double()
+        S = S_last.to(self.dev).double()
+        ms, Ss = [], []
+        for _ in range(h):
+            m = m @ Phi.T
+            S = Phi @ S @ Phi.T + Q
+            ms.append(m)
+            Ss.append(S)
+        return torch.stack(ms).float().contiguous(), torch.stack(Ss).float().contiguous()

@@ -17,6 +17,7 @@ return this rank's own slices without communication.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional
 
@@ -204,6 +205,127 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
     def local_covs(self) -> torch.Tensor:
         """This rank's slices (n, T_local, d, d) of the current covariances."""
         return self._ensure_engine().covs_local().detach().to("cpu").contiguous()
+
+    # ---------------- posterior-predictive checks and forecasts (extensions) ----------------
+    # The reference's calibration_error / compute_coverage /
+    # temporal_prediction_metrics (src/utils/metrics.py:350-518) take predictive
+    # intervals of the dyads; these calls produce them from (X_mean, X_cov) on the
+    # device (ame_predict), as per-time-step sums or as dense blocks.
+    @staticmethod
+    def _thresholds(levels):
+        """zsq = Phi^-1((1 + p) / 2)^2 (marginal) and csq = -2 ln(1 - p) (joint, 2 dof)."""
+        from statistics import NormalDist
+        from .. import _lib
+        levels = tuple(float(p) for p in levels)
+        if len(levels) > _lib.AME_PREDICT_MAX_LEVELS:
+            raise ValueError(f"at most {_lib.AME_PREDICT_MAX_LEVELS} levels (got {len(levels)})")
+        for p in levels:
+            if not 0.0 < p < 1.0:
+                raise ValueError(f"coverage level {p} outside (0, 1)")
+        nd = NormalDist()
+        return (levels, [nd.inv_cdf((1.0 + p) / 2.0) ** 2 for p in levels],
+                [-2.0 * math.log1p(-p) for p in levels])
+
+    @staticmethod
+    def _check_dict(sums, levels):
+        """The public dictionary from per-slice sum rows (S, AME_PREDICT_SUMS), fp64 numpy."""
+        s = sums.detach().to("cpu", torch.float64).numpy()
+        L = len(levels)
+        pairs = s[:, 0].copy()
+        cnt = s[:, 9:9 + 3 * L].reshape(s.shape[0], L, 3)
+        return {"levels": levels, "pairs": pairs, "log_score": s[:, 1].copy(),
+                "mahalanobis": s[:, 2].copy(), "z2": s[:, 3:5].copy(), "mean_var": s[:, 5:7].copy(),
+                "sq_err": s[:, 7:9].copy(), "coverage": cnt[:, :, :2] / pairs[:, None, None],
+                "joint_coverage": cnt[:, :, 2] / pairs[:, None]}
+
+    def _range(self, sel, size, what):
+        """A contiguous index range from None, an int, a range or a slice."""
+        if sel is None:
+            return 0, size
+        if isinstance(sel, int):
+            k = sel + size if -size <= sel < 0 else sel
+            sel = range(k, k + 1)
+        if isinstance(sel, slice):
+            sel = range(*sel.indices(size))
+        if not isinstance(sel, range) or sel.step != 1 or len(sel) < 1 or sel.start < 0 or sel.stop > size:
+            raise ValueError(f"{what} must be a non-empty contiguous range within [0, {size})")
+        return sel.start, sel.stop
+
+    def _predict_engine(self):
+        eng = self._ensure_engine()
+        eng.discard_speculation()
+        return eng
+
+    def predictive_check(self, levels=(0.5, 0.9, 0.95), include_noise=True) -> dict:
+        """Score the observed network against the posterior-predictive moments of
+        every dyad, in-sample.  fp64 arrays of length T: ``pairs``, ``log_score``
+        (sum of log N(y_ij; E mu_ij, Sigma_ij) over pairs i < j), ``mahalanobis``,
+        ``z2`` (T, 2), ``mean_var`` (T, 2), ``sq_err`` (T, 2), ``coverage``
+        (T, L, 2) and ``joint_coverage`` (T, L) as fractions, and ``levels``.
+        include_noise=False scores against the credible region of the mean.
+        Time-sharded: a collective, every rank returns all T steps."""
+        levels, zsq, csq = self._thresholds(levels)
+        eng = self._predict_engine()
+        sums, _ = eng.predict(eng.x_a, eng.cov, Yt=eng.Yt, include_noise=include_noise,
+                              zsq=zsq, csq=csq)
+        if getattr(self, "_halo", None) is not None:
+            sums = self._halo.gather_time(sums.unsqueeze(0), 1)[0]
+        return self._check_dict(sums, levels)
+
+    def _dense(self, eng, x, cov, rows, cols, include_noise, max_elements):
+        i0, i1 = self._range(rows, self.n, "rows")
+        j0, j1 = self._range(cols, self.n, "cols")
+        count = int(x.shape[0]) * (i1 - i0) * (j1 - j0) * 5
+        if count > int(max_elements):
+            raise ValueError(f"{count} output floats exceed max_elements={int(max_elements)}; "
+                             "ask for fewer times, rows or columns")
+        _, dense = eng.predict(x, cov, include_noise=include_noise, block=(i0, i1, j0, j1))
+        dense = dense.permute(1, 2, 0, 3).to("cpu")
+        return dense[..., :2].contiguous(), dense[..., 2:].contiguous()
+
+    def predict_dyads(self, times, rows=None, cols=None, include_noise=True, max_elements=2 ** 27):
+        """Dense predictive moments ``(mean, second)`` on the CPU: (ni, nj, S, 2)
+        = E[mu_ij] and (ni, nj, S, 3) = Var of entry 0, Var of entry 1 and their
+        covariance (with model.R added when include_noise).  ``times`` is an int
+        or a slice, ``rows`` / ``cols`` contiguous ranges or slices.  The diagonal
+        holds compute_mean's means and NaN second moments."""
+        eng = self._predict_engine()
+        if getattr(self, "_halo", None) is not None:
+            raise NotImplementedError("predict_dyads is not available on a time-sharded run: "
+                                      "score with predictive_check, or fit on one process")
+        t0, t1 = self._range(times, self.T, "times")
+        return self._dense(eng, eng.x_a[t0:t1], eng.cov[t0:t1], rows, cols, include_noise, max_elements)
+
+    def _forecast_states(self, n_steps):
+        eng = self._predict_engine()
+        if getattr(self, "_halo", None) is None:
+            m, S = eng.x_a[-1], eng.cov[-1]
+        else:   # collective getters: every rank reads the last slice and computes the same
+            m, S = self.X_mean[:, -1], self.X_cov[:, -1]
+        return eng, eng.forecast_states(m, S, n_steps)
+
+    def forecast(self, n_steps: int = 1):
+        """h-step forecast of the states from the last fitted slice, ``(X_pred
+        (n, h, d), S_pred (n, h, d, d))`` on the CPU: m_k = Phi m_{k-1}, S_k = Phi
+        S_{k-1} Phi' + Q (the means are naive_mf.py:386-396's predict_forward)."""
+        _, (m, S) = self._forecast_states(n_steps)
+        return m.permute(1, 0, 2).to("cpu").contiguous(), S.permute(1, 0, 2, 3).to("cpu").contiguous()
+
+    def forecast_check(self, Y_future, levels=(0.5, 0.9, 0.95), include_noise=True) -> dict:
+        """predictive_check of held-out steps: ``Y_future`` (n, n, h, 2) scored
+        against the h-step forecast; the same dictionary, of length h."""
+        levels, zsq, csq = self._thresholds(levels)
+        Y_future = torch.as_tensor(Y_future)
+        eng, (m, S) = self._forecast_states(int(Y_future.shape[2]) if Y_future.dim() == 4 else 1)
+        Yt = eng.pack_future(Y_future)
+        sums, _ = eng.predict(m, S, Yt=Yt, include_noise=include_noise, zsq=zsq, csq=csq)
+        return self._check_dict(sums, levels)
+
+    def forecast_dyads(self, n_steps: int = 1, rows=None, cols=None, include_noise=True,
+                       max_elements=2 ** 27):
+        """predict_dyads of the h-step forecast: (ni, nj, h, 2) and (ni, nj, h, 3)."""
+        eng, (m, S) = self._forecast_states(n_steps)
+        return self._dense(eng, m, S, rows, cols, include_noise, max_elements)
 
     def get_variational_means(self) -> torch.Tensor:
         return self.X_mean
