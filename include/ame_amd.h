@@ -101,7 +101,12 @@ enum ame_wait_site {
 
 /* Sweep kernels.  Concrete kinds (what ame_sweep launches):
  *   AME_SWEEP_V3          one 512-thread workgroup per slice (solver wave + 7
- *                         helper waves, slice (U,V) in registers/LDS); d <= 64
+ *                         helper waves, slice (U,V) in registers/LDS); the slice's
+ *                         state must fit one CU's 160 KiB LDS, which holds for
+ *                         r <= 23 only: n <= 3456 up to r = 6, falling to
+ *                         n <= 1344 at r = 16, 896 at r = 20, 768 at r = 21,
+ *                         384 at r = 22 and 128 at r = 23 (ame_sweep_kind tells;
+ *                         tests/test_every_r_guard.py pins the bound)
  *   AME_SWEEP_V2_LDS      one 256-thread workgroup per slice, (U,V) block in LDS
  *   AME_SWEEP_V2_HBM      same, (U,V) block in HBM (args.work)
  *   AME_SWEEP_V2_WORKERS  v2 plus seven GEMV worker workgroups per slice holding

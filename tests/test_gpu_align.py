@@ -54,14 +54,34 @@ def test_align_keeps_fp64_dtype(gpu_device):
     assert lat.dtype == torch.float64
 
 
-@pytest.mark.parametrize("n,T,r", [(1024, 16, 16), (500, 6, 32), (77, 3, 1)])
-def test_align_vs_oracle_large(n, T, r, gpu_device):
-    """Device-resident inputs at config sizes against the fp64 oracle."""
-    from ame_amd.utils import align_temporal_states, compute_alignment_error
-    rng = np.random.default_rng(n + r)
+BASE_ORACLE_SHAPES = ((1024, 16, 16), (500, 6, 32), (77, 3, 1))
+# every other compiled r at the small shape (two partial blocks of nodes)
+ORACLE_SHAPES = BASE_ORACLE_SHAPES + tuple(
+    (77, 3, r) for r in range(1, 33) if r not in {s[2] for s in BASE_ORACLE_SHAPES})
+
+
+# seed n + r puts one U row of (77, 3, 21) within 3.5e-7 (|x|^2 + |t|^2) of a
+# sign tie, inside what fp32 sums of 21 squares can blur (1.4e-6 required by
+# tests/test_align_oracle.py): that shape draws from another seed
+SEED_SHIFT = {(77, 3, 21): 1000}
+
+
+def oracle_inputs(n, T, r):
+    """The inputs of test_align_vs_oracle_large; tests/test_align_oracle.py
+    checks on the CPU that no row of them sits on a sign tie."""
+    rng = np.random.default_rng(n + r + SEED_SHIFT.get((n, T, r), 0))
     Xt = rng.standard_normal((n, T, 2 + 2 * r)).astype(np.float32)
     Xe = (Xt[:, :, ::-1] * 0.9 + 0.3 * rng.standard_normal(Xt.shape)).astype(np.float32)
-    Xe_d = torch.from_numpy(np.ascontiguousarray(Xe)).to(gpu_device)
+    return np.ascontiguousarray(Xe), Xt
+
+
+@pytest.mark.parametrize("n,T,r", ORACLE_SHAPES)
+def test_align_vs_oracle_large(n, T, r, gpu_device):
+    """Device-resident inputs at config sizes, and at every compiled r, against
+    the fp64 oracle."""
+    from ame_amd.utils import align_temporal_states, compute_alignment_error
+    Xe, Xt = oracle_inputs(n, T, r)
+    Xe_d = torch.from_numpy(Xe).to(gpu_device)
     Xt_d = torch.from_numpy(Xt).to(gpu_device)
     for each in (True, False):
         got = align_temporal_states(Xe_d, Xt_d, r, align_each_time=each)

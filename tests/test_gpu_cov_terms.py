@@ -72,7 +72,15 @@ def _check(got, ref):
     assert err.max() <= 1e-10, err.max()
 
 
-@pytest.mark.parametrize("r", [1, 3, 8, 12, 16, 20, 24, 28, 32])
+# Every compiled r: the column-per-lane form changes with r (LPM lanes per
+# matrix, 4 at r = 2; the no-prefetch code for B = 2r > 32 with one covariance
+# per wave serves r = 17, 18, 19 only), and in the MFMA form an odd r >= 21 puts
+# a 4-column panel across the boundary between real columns and identity padding.
+SPD_R = tuple(range(1, 33))
+INDEFINITE_R = (2, 4, 6, 16, 17, 19, 21, 23, 24, 31, 32)
+
+
+@pytest.mark.parametrize("r", SPD_R)
 @pytest.mark.parametrize("t_begin", [0, 1])
 def test_cov_terms_random_spd(r, t_begin, gpu_device):
     rng = np.random.default_rng(100 + r + 7 * t_begin)
@@ -84,7 +92,7 @@ def test_cov_terms_random_spd(r, t_begin, gpu_device):
     _check(got, _ref(cov, consts, t_begin))
 
 
-@pytest.mark.parametrize("r", [4, 16, 24, 32])
+@pytest.mark.parametrize("r", INDEFINITE_R)
 def test_cov_terms_indefinite(r, gpu_device):
     """Negative determinants (one negative eigenvalue in the complement, or a
     negative-determinant (a,b) block): nan, as torch.logdet."""

@@ -34,12 +34,16 @@ def _params(m, dtype=np.float64):
 
 
 def _check_vs_oracle(n, T, r, method, lr, dev, iters=2, model_hook=None, data_hook=None,
-                     check_terms=False, **opts):
+                     check_terms=False, fp32_cap=None, **opts):
     """`model_hook(model)` is called with the freshly built model before data
     generation and may overwrite its six parameter attributes (PKEYS);
     `data_hook(model)` after it and may edit Y.  Both sides follow: the oracle's
     `params` and Y are read from the model below.  `check_terms` also holds each
-    of the four ELBO terms of the final state to 5e-6 |ELBO|."""
+    of the four ELBO terms of the final state to 5e-6 |ELBO|.  `fp32_cap`
+    (default: none) bounds the fp32 allowance itself: the fp32 oracle's
+    deviation from the fp64 one must stay within fp32_cap * max(1, max|mean|),
+    asserted from the CPU oracle alone before the device result is looked at, so
+    a case whose fp32 restatement drifts cannot widen the kernel's bound."""
     import ame_oracle as O
     from ame_amd import TemporalAMEModel
     m = TemporalAMEModel(n, T, r, seed=7)
@@ -56,6 +60,10 @@ def _check_vs_oracle(n, T, r, method, lr, dev, iters=2, model_hook=None, data_ho
     ref = O.fit(m.Y.numpy().astype(np.float64), Xm, Xc, params, method, lr, iters, 0.0)
     O.fit(m.Y.numpy(), Xm32, Xc32, _params(m, np.float32), method, lr, iters, 0.0)
     fp32_err = np.abs(Xm32.astype(np.float64) - Xm).max()
+    if fp32_cap is not None:
+        cap = fp32_cap * max(1.0, np.abs(Xm).max())
+        print(f"fp32 cap {n}x{T} r={r} {method}: fp32 restatement {fp32_err:.3e} of cap {cap:.3e}")
+        assert fp32_err <= cap, (fp32_err, cap)
     h = vi.fit(max_iter=iters, tolerance=0.0, verbose=False)
     err = np.abs(vi.X_mean.numpy() - Xm).max()
     # fp32 allowance: the kernel's error may exceed the fp32 restatement's own

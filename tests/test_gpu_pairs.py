@@ -26,13 +26,21 @@ def _sums(vi, v1):
     return out
 
 
-@pytest.mark.parametrize("n,T,r,swap", [
+BASE_SHAPES = (
     (64, 3, 16, True), (130, 2, 16, True), (200, 3, 8, False), (256, 4, 32, True),
     (1024, 8, 16, True), (1024, 2, 16, False), (2, 3, 1, True), (98, 2, 5, True),
     (192, 5, 3, False), (4096, 1, 32, True),
     # odd n: rows padded to even length (ame_ystride), the v2 kernel's DMA
     # chunks stay 16-byte aligned and the pad column is masked
-    (97, 3, 5, True), (257, 2, 16, False), (1023, 2, 16, True), (3, 2, 2, True)])
+    (97, 3, 5, True), (257, 2, 16, False), (1023, 2, 16, True), (3, 2, 2, True))
+# every other compiled r (the MFMA K padding RP takes 12, 20, 24, 28 only
+# here): n = 70 is two column tiles with a 6-wide edge tile, in both tile walks
+EVERY_R_SHAPES = tuple((70, 2, r, r % 2 == 0) for r in range(1, 33)
+                       if r not in {s[2] for s in BASE_SHAPES})
+SHAPES = BASE_SHAPES + EVERY_R_SHAPES
+
+
+@pytest.mark.parametrize("n,T,r,swap", SHAPES)
 def test_pairs_v2_matches_v1_and_oracle(n, T, r, swap, gpu_device):
     import ame_oracle as O
     from ame_amd import TemporalAMEModel, TemporalAMEStructuredMFVI

@@ -1,11 +1,11 @@
 """ame_predict on the GPU (posterior-predictive dyad moments, scoring sums,
 forecasts) against the fp64 reference tests/predictive_ref.py.
 
-Elementwise tolerance.  predictive_ref.DELTA0 = 2.1e-6 is the largest error of
+Elementwise tolerance.  predictive_ref.DELTA0 = 2.3e-6 is the largest error of
 an np.float32 evaluation of the same formulas (products and sums one after
-another) against the fp64 reference over the inputs used here (measured 2.185e-6
-at (97, 2, 32), re-measured by tests/test_predictive_ref.py), relative to the
-dyad's sum of |products|.  The kernel's bound is TOL = 4 x DELTA0 = 8.4e-6 of
+another) against the fp64 reference over the inputs used here (measured 2.366e-6
+at (65, 2, 31), re-measured by tests/test_predictive_ref.py), relative to the
+dyad's sum of |products|.  The kernel's bound is TOL = 4 x DELTA0 = 9.2e-6 of
 that sum (the margin is for the MFMA chain's different summation order over up
 to ~2200 terms).  Sums of non-negative summands (slots 2-8) are held to 5e-6
 relative and the log score to 5e-6 x sum|summand| (the fp32-vs-fp64 bound of
@@ -123,7 +123,7 @@ def _assert_sums(check, ref, levels):
                 assert lo <= round(cnt) <= hi and abs(cnt - round(cnt)) < 1e-6, (t, l, name, cnt, lo, hi)
 
 
-@pytest.mark.parametrize("shape", R.GPU_SHAPES, ids=IDS)
+@pytest.mark.parametrize("shape", R.GPU_SHAPES + R.GPU_SHAPES_EVERY_R, ids=IDS)
 def test_dense_moments_match_reference(shape, gpu_device):
     c = _case(shape)
     n, T, r = shape
@@ -155,7 +155,7 @@ def test_noise_adds_exactly_R(shape, gpu_device):
         assert (np.abs(a - b - add) <= 2.0 ** -23 * np.maximum(np.abs(a), abs(add))).all()
 
 
-@pytest.mark.parametrize("shape", R.GPU_SHAPES, ids=IDS)
+@pytest.mark.parametrize("shape", R.GPU_SHAPES + R.GPU_SHAPES_EVERY_R, ids=IDS)
 def test_scoring_sums_match_reference(shape, gpu_device):
     c = _case(shape)
     assert c["check"]["levels"] == LEVELS

@@ -7,8 +7,8 @@ The elementwise tolerance of the GPU tests (tests/test_gpu_predictive.py) is
 derived here: DELTA0 is the largest error, over the GPU tests' inputs and
 dyads, of an np.float32 evaluation of the formulas (products and sums one after
 another) against the fp64 reference, relative to the dyad's sum of |products|;
-the kernel's bound is 4 x DELTA0.  Measured: 2.185e-6 (at (97, 2, 32)); the
-constant predictive_ref.DELTA0 = 2.1e-6 rounds it down, bound 8.4e-6.
+the kernel's bound is 4 x DELTA0.  Measured: 2.366e-6 (at (65, 2, 31)); the
+constant predictive_ref.DELTA0 = 2.3e-6 rounds it down, bound 9.2e-6.
 """
 import functools
 
@@ -18,11 +18,14 @@ import pytest
 import predictive_ref as R
 
 
+DELTA0_SHAPES = R.GPU_SHAPES + R.GPU_SHAPES_EVERY_R
+
+
 @functools.lru_cache(maxsize=None)
 def delta0():
     """Largest fp32-vs-fp64 relative error over the GPU tests' inputs."""
     worst = 0.0
-    for n, T, r in R.GPU_SHAPES:
+    for n, T, r in DELTA0_SHAPES:
         m, S = R.make_state(n, T, r)
         for t in range(T):
             worst = max(worst, R.f32_relative_error(m[:, t], S[:, t], r))
