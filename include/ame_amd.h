@@ -29,6 +29,9 @@
  *                     covariances), scored against the observed network
  *                     (the input metrics.py:350-518 expects and nothing there
  *                     produces), as per-slice sums or a dense block.
+ *   ame_mstep_stats   replaces nothing in the reference: the sufficient
+ *                     statistics of q from which the closed-form M-step of
+ *                     variational EM re-estimates Phi, Q, R, Sigma and Psi.
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -344,6 +347,43 @@ int ame_predict(const ame_dims* dims, const ame_predict_args* args, void* stream
 /* Scratch doubles ame_predict needs (per-node feature rows and per-workgroup
  * partials; nothing of size n^2 per slice beyond 21 doubles per 64 x 64 tile). */
 long long ame_predict_work_size(const ame_dims* dims);
+
+/* ---- M-step sufficient statistics (variational EM) ---------------------------
+ * Replaces nothing the reference computes: it never estimates Phi, Q, R, Sigma
+ * or Psi.  With q(x_it) = N(m_it, S_it) independent across nodes and time and
+ * E_it = m_it m_it' + S_it, the expected complete-data log-likelihood
+ *   F = -1/2 [ Np log|R| + tr(R^-1 Rss) ] - 1/2 [ n log|S0| + tr(S0^-1 A0) ]
+ *       -1/2 [ n (T-1) log|Q| + tr(Q^-1 (A11 - Phi A10' - A10 Phi' + Phi A00 Phi')) ]
+ * depends on q only through
+ *   A0  = sum_i E_i0                 A11 = sum_i sum_{t>=1} E_it
+ *   A00 = sum_i sum_{t>=1} E_i,t-1   A10 = sum_i sum_{t>=1} m_it m_i,t-1'
+ *   Rss = sum_t sum_{i<j} ( e e' + [[V0(i,j), C01(i,j)], [C01(i,j), V0(j,i)]] )
+ * with e = y_ij - E[mu_ij], V0 and C01 as under ame_predict (no noise added) and
+ * the upper triangle Yt[t][i][j] as the observation.  ame_mstep_stats returns
+ * them per local slice; the host adds slices in global time order in fp64:
+ *   state [t][0] = P_t = sum_i E_it,   state [t][1] = C_t = sum_i m_it m_i,t-1'
+ *         (C_t = 0 at global slice 0; d x d row-major fp64)
+ *         A0 = P_0, A11 = sum_{t>=1} P_t, A00 = sum_{t<=T-2} P_t, A10 = sum_{t>=1} C_t
+ *   dyad  [t] = { pairs, Rss00, Rss11, Rss01 } of the slice
+ * State pass: one workgroup per (slice, chunk of 32 nodes) streams the chunk's
+ * covariances once, every product and sum in fp64, and a second kernel adds the
+ * chunk partials in chunk order.  The chunk size is a constant, so a slice's
+ * row has the same bits under any time sharding and any split of the slices
+ * over calls.  Dyad pass: ame_predict's feature rows and five tile products
+ * with an fp64 epilogue and a fixed-order reduce.  No atomics, no spin. */
+typedef struct ame_mstep_args {
+    const float* x;          /* [T_local][n][d] means */
+    const float* cov;        /* [T_local][n][d][d] */
+    const float* prev_final; /* [n][d] means of global slice t_begin-1; required iff t_begin > 0 */
+    const float* Yt;         /* packed observations (ame_pack_y), or NULL: no dyad statistics */
+    double* state;           /* [T_local][2][d][d] fp64: P_t, C_t, or NULL */
+    double* dyad;            /* [T_local][4] fp64: pairs, Rss00, Rss11, Rss01, or NULL */
+    double* work;            /* >= ame_mstep_work_size() doubles */
+} ame_mstep_args;
+int ame_mstep_stats(const ame_dims* dims, const ame_mstep_args* args, void* stream);
+/* Scratch doubles ame_mstep_stats needs (chunk partials, feature rows, tile
+ * partials), -1 on bad dims. */
+long long ame_mstep_work_size(const ame_dims* dims);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

@@ -77,9 +77,14 @@ class ame_predict_args(ctypes.Structure):
                 ("i0", c_int32), ("i1", c_int32), ("j0", c_int32), ("j1", c_int32), ("work", c_vp)]
 
 
+class ame_mstep_args(ctypes.Structure):
+    _fields_ = [("x", c_vp), ("cov", c_vp), ("prev_final", c_vp), ("Yt", c_vp), ("state", c_vp),
+                ("dyad", c_vp), ("work", c_vp)]
+
+
 # every symbol include/ame_amd.h declares (checked by tests/test_capi.py)
 EXPORTS = ("ame_pack_y", "ame_pack_y_size", "ame_sweep", "ame_sweep_kind", "ame_sweep_work_size", "ame_sweep_orders_slices", "ame_sweep_max_slices", "ame_sweep_slice_workgroups", "ame_sweep_lds_bytes", "ame_cov",
-           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_host_register", "ame_host_unregister",
+           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_host_register", "ame_host_unregister",
            "ame_stream_create_cu_range", "ame_stream_destroy",
            "ame_peer_alloc", "ame_peer_free", "ame_peer_open", "ame_peer_close",
            "ame_peer_probe", "ame_peer_read_u64", "ame_peer_clear",
@@ -111,6 +116,10 @@ def _declare(L):
     L.ame_predict.restype = ctypes.c_int
     L.ame_predict_work_size.argtypes = [P(ame_dims)]
     L.ame_predict_work_size.restype = ctypes.c_longlong
+    L.ame_mstep_stats.argtypes = [P(ame_dims), P(ame_mstep_args), c_vp]
+    L.ame_mstep_stats.restype = ctypes.c_int
+    L.ame_mstep_work_size.argtypes = [P(ame_dims)]
+    L.ame_mstep_work_size.restype = ctypes.c_longlong
     L.ame_debug_selftest.argtypes = [c_vp, c_vp]
     L.ame_debug_selftest.restype = ctypes.c_int
     if hasattr(L, "ame_debug_occupy"):   # diagnostic; absent from older A/B builds

@@ -25,6 +25,12 @@ long long ame_align_partials_count(int n, int T);
 int ame_predict_dispatch(const ame_dims*, const ame_predict_args*, hipStream_t);
 long long ame_predict_work_doubles(const ame_dims*);
 long long ame_predict_max_blocks(const ame_dims*, const ame_predict_args*);
+int ame_mstep_state_dispatch(const ame_dims*, const ame_mstep_args*, hipStream_t);
+long long ame_mstep_state_work_doubles(const ame_dims*);
+long long ame_mstep_state_blocks(const ame_dims*);
+int ame_mstep_dyad_dispatch(const ame_dims*, const ame_mstep_args*, double* work, hipStream_t);
+long long ame_mstep_dyad_work_doubles(const ame_dims*);
+long long ame_mstep_dyad_blocks(const ame_dims*);
 int ame_pack_dispatch(const float*, float*, const ame_dims*, unsigned long long*, hipStream_t);
 
 static thread_local char g_err[512] = "";
@@ -446,6 +452,30 @@ int ame_predict(const ame_dims* dims, const ame_predict_args* a, void* stream) {
         return fail("ame_predict: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
                     dims->T_local, dims->n);
     return launched(ame_predict_dispatch(dims, a, (hipStream_t)stream), "predict");
+}
+
+long long ame_mstep_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_mstep_state_work_doubles(dims) + ame_mstep_dyad_work_doubles(dims);
+}
+
+int ame_mstep_stats(const ame_dims* dims, const ame_mstep_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a || !a->x || !a->cov || !a->work) return fail("ame_mstep_stats: NULL buffer (x, cov, work)");
+    if (!a->state && !a->dyad) return fail("ame_mstep_stats: state and dyad are both NULL");
+    if (a->dyad && !a->Yt) return fail("ame_mstep_stats: dyad statistics need the observations Yt (NULL)");
+    if (a->state && dims->t_begin > 0 && !a->prev_final)
+        return fail("ame_mstep_stats: t_begin=%d > 0 needs prev_final", dims->t_begin);
+    if ((a->state && ame_mstep_state_blocks(dims) > 0x7FFFFFFFLL) ||
+        (a->dyad && ame_mstep_dyad_blocks(dims) > 0x7FFFFFFFLL))
+        return fail("ame_mstep_stats: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    if (a->state)
+        if (int e = launched(ame_mstep_state_dispatch(dims, a, (hipStream_t)stream), "mstep_state")) return e;
+    if (a->dyad)
+        return launched(ame_mstep_dyad_dispatch(dims, a, a->work + ame_mstep_state_work_doubles(dims),
+                                                (hipStream_t)stream), "mstep_dyad");
+    return 0;
 }
 
 static int check_align(int n, int T, int r) {

@@ -7,7 +7,8 @@
     int ame_sweep_dispatch_p##P(const ame_dims*, const ame_sweep_args*, hipStream_t);     \
     int ame_sweep_blocks_per_cu_p##P(int, int, int);                                      \
     int ame_sweep_workers_fit_p##P(const ame_dims*, int);                                 \
-    int ame_predict_dispatch_p##P(const ame_dims*, const ame_predict_args*, hipStream_t);
+    int ame_predict_dispatch_p##P(const ame_dims*, const ame_predict_args*, hipStream_t);     \
+    int ame_mstep_dyad_dispatch_p##P(const ame_dims*, const ame_mstep_args*, double*, hipStream_t);
 AME_DECL_SWEEP(0)
 AME_DECL_SWEEP(1)
 AME_DECL_SWEEP(2)
@@ -62,5 +63,12 @@ int ame_predict_dispatch(const ame_dims* dm, const ame_predict_args* a, hipStrea
         case 0: return ame_predict_dispatch_p0(dm, a, st);
         case 1: return ame_predict_dispatch_p1(dm, a, st);
         default: return ame_predict_dispatch_p2(dm, a, st);
+    }
+}
+int ame_mstep_dyad_dispatch(const ame_dims* dm, const ame_mstep_args* a, double* work, hipStream_t st) {
+    switch (dm->r % 3) {
+        case 0: return ame_mstep_dyad_dispatch_p0(dm, a, work, st);
+        case 1: return ame_mstep_dyad_dispatch_p1(dm, a, work, st);
+        default: return ame_mstep_dyad_dispatch_p2(dm, a, work, st);
     }
 }

@@ -27,6 +27,8 @@
 //    of 4) and runs the epilogue on them: scoring in fp64 against Y, read once
 //    from the upper triangle (MODE 0, tiles I <= J), or the dense block (MODE 1).
 // K3 ame_predict_final_kernel: fixed-order sum of a slice's tile partials.
+// MODE 2 of K2 (ame_mstep_stats): the same tiles and products, with the M-step's
+//    residual second moments as the epilogue and ame_mstep_dyad_final_kernel as K3.
 // No atomics, no spin, no O(n^2) intermediate.
 #include <type_traits>
 
@@ -38,6 +40,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define AME_PKB 32       // K chunk in floats
 #define AME_PLD 34       // LDS row stride: 2 li + lq hits 32 distinct banks per half wave
 #define AME_PNS AME_PREDICT_SUMS
+#define AME_MS_DYAD 4    // M-step dyad statistics per slice: pairs, Rss00, Rss11, Rss01
 
 __host__ __device__ constexpr int ame_pad4(int k) { return (k + 3) & ~3; }
 // floats of one node's feature row for latent dim r
@@ -177,6 +180,14 @@ ame_predict_pairs_kernel(PredictParams p) {
         ilim = p.i1;
         jlim = p.j1;
     }
+    if (MODE == 2) {   // M-step dyad statistics: MODE 0's upper-triangle tiles
+        const int nb = (n + AME_PT - 1) / AME_PT;
+        int I = 0, rem = tile;
+        while (rem >= nb - I) { rem -= nb - I; ++I; }
+        I0 = I * AME_PT;
+        J0 = (I + rem) * AME_PT;
+        ilim = jlim = n;
+    }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int li = lane & 15, lq = lane >> 4;
 
@@ -254,6 +265,36 @@ ame_predict_pairs_kernel(PredictParams p) {
     product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
 
     // accumulator element (s, g) of this lane: i = I0 + 16 w + 4 lq + g, j = J0 + 16 s + li
+    if (MODE == 2) {   // pairs, e0^2 + V0(i,j), e1^2 + V0(j,i), e0 e1 + C01 (no noise), fp64
+        double sm[AME_MS_DYAD];
+#pragma unroll
+        for (int q = 0; q < AME_MS_DYAD; ++q) sm[q] = 0.0;
+        const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = J0 + 16 * s + li;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = I0 + 16 * w + 4 * lq + g;
+                if (i < n && j < n && i < j) {
+                    const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
+                    const double e0 = (double)y.x - (double)acc[0][s][g];
+                    const double e1 = (double)y.y - (double)acc[1][s][g];
+                    sm[0] += 1.0;
+                    sm[1] += e0 * e0 + (double)acc[2][s][g];
+                    sm[2] += e1 * e1 + (double)acc[3][s][g];
+                    sm[3] += e0 * e1 + (double)acc[4][s][g];
+                }
+            }
+        }
+        block_sum<AME_MS_DYAD>(sm, red);
+        if (threadIdx.x == 0) {
+            double* o = p.partial + ((size_t)tl * ntile + tile) * AME_MS_DYAD;
+#pragma unroll
+            for (int q = 0; q < AME_MS_DYAD; ++q) o[q] = sm[q];
+        }
+        return;
+    }
     if (MODE == 0) {
         double sm[AME_PNS];
 #pragma unroll
@@ -345,6 +386,25 @@ ame_predict_final_kernel(const double* __restrict__ partial, int ntile, double* 
     }
 }
 
+// K3 of the M-step dyad statistics: a slice's tile partials in tile order
+static __global__ void __launch_bounds__(AME_NT)
+ame_mstep_dyad_final_kernel(const double* __restrict__ partial, int ntile, double* __restrict__ dyad) {
+    __shared__ double red[4 * AME_MS_DYAD];
+    const double* ps = partial + (size_t)blockIdx.x * ntile * AME_MS_DYAD;
+    double v[AME_MS_DYAD];
+#pragma unroll
+    for (int q = 0; q < AME_MS_DYAD; ++q) v[q] = 0.0;
+    for (int b = threadIdx.x; b < ntile; b += AME_NT) {
+#pragma unroll
+        for (int q = 0; q < AME_MS_DYAD; ++q) v[q] += ps[(size_t)b * AME_MS_DYAD + q];
+    }
+    block_sum<AME_MS_DYAD>(v, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < AME_MS_DYAD; ++q) dyad[(size_t)blockIdx.x * AME_MS_DYAD + q] = v[q];
+    }
+}
+
 static inline long long predict_tri_tiles(int n) {
     const long long nb = (n + AME_PT - 1) / AME_PT;
     return nb * (nb + 1) / 2;
@@ -371,6 +431,15 @@ long long ame_predict_max_blocks(const ame_dims* dm, const ame_predict_args* a) 
         m = b > m ? b : m;
     }
     return m;
+}
+
+// the dyad part of ame_mstep_stats' work buffer: feature rows, then tile partials
+long long ame_mstep_dyad_work_doubles(const ame_dims* dm) {
+    return predict_feat_doubles(dm) + (long long)dm->T_local * predict_tri_tiles(dm->n) * AME_MS_DYAD;
+}
+long long ame_mstep_dyad_blocks(const ame_dims* dm) {
+    const long long a = (long long)dm->T_local * dm->n, b = (long long)dm->T_local * predict_tri_tiles(dm->n);
+    return a > b ? a : b;
 }
 #endif
 
@@ -415,6 +484,46 @@ static int launch_predict(const ame_dims* dm, const ame_predict_args* a, hipStre
                            dim3(AME_NT), 0, st, p);
     }
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// MODE 2: the feature kernel and the five tile products of ame_predict with the
+// M-step epilogue; `work` is the dyad part of ame_mstep_args.work
+template <int R>
+static int launch_mstep_dyad(const ame_dims* dm, const ame_mstep_args* a, double* work, hipStream_t st) {
+    const int S = dm->T_local, n = dm->n;
+    float* feat = (float*)work;
+    hipLaunchKernelGGL(ame_predict_feat_kernel<R>, dim3((unsigned)((long long)S * n)), dim3(AME_NT), 0, st,
+                       a->x, a->cov, feat);
+    PredictParams p;
+    p.n = n;
+    p.S = S;
+    p.ny = ame_ystride(n);
+    p.n_levels = 0;
+    p.i0 = p.i1 = p.j0 = p.j1 = 0;
+    p.ntj = 1;
+    p.feat = feat;
+    p.Yt = a->Yt;
+    p.n00 = p.n01 = p.n11 = 0.0;
+    for (int l = 0; l < AME_PREDICT_MAX_LEVELS; ++l) p.zsq[l] = p.csq[l] = 0.0;
+    p.partial = work + predict_feat_doubles(dm);
+    p.dense = nullptr;
+    p.ntile = (int)predict_tri_tiles(n);
+    hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 2>), dim3((unsigned)((long long)S * p.ntile)),
+                       dim3(AME_NT), 0, st, p);
+    hipLaunchKernelGGL(ame_mstep_dyad_final_kernel, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
+                       p.ntile, a->dyad);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int AME_PFN(ame_mstep_dyad_dispatch)(const ame_dims* dm, const ame_mstep_args* a, double* work,
+                                     hipStream_t st) {
+    switch (dm->r) {
+#define X(RR) \
+    case RR: return launch_mstep_dyad<RR>(dm, a, work, st);
+        AME_FOR_EACH_R(X)
+#undef X
+        default: return -1;
+    }
 }
 
 int AME_PFN(ame_predict_dispatch)(const ame_dims* dm, const ame_predict_args* a, hipStream_t st) {

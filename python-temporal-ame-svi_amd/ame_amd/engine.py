@@ -886,6 +886,61 @@ class DeviceEngine:
         self._elbo_stream_end(st)
         return sums, dense
 
+    # ------------------------------------------------------------------
+    # M-step sufficient statistics and new constants (ame_mstep_stats)
+    # ------------------------------------------------------------------
+    def mstep_stats(self):
+        """Per-slice sufficient statistics of the current state for the M-step:
+        ``state`` [T_local][2][d][d] (P_t, C_t) and ``dyad`` [T_local][4] (pairs,
+        Rss00, Rss11, Rss01), fp64 on the device.  Whole slices at a time within
+        the scratch budget of predict(); a slice's row does not depend on the
+        split.  Time-sharded: a collective (the left neighbour's last means)."""
+        self.discard_speculation()
+        n, d, sh = self.n, self.d, self.shard
+        TL = sh.T_local
+        prev_final = self.halo.prev_final(self) if self.halo is not None else None
+        one = _lib.ame_dims(n, self.r, 1, 0, 1, self.vcode)
+        per = int(self.L.ame_mstep_work_size(ctypes.byref(one)))
+        if per < 0:
+            _lib.check(-1, "ame_mstep_work_size")
+        chunk = max(1, min(TL, self.PREDICT_WORK_DOUBLES // per))
+        dims = _lib.ame_dims(n, self.r, chunk, 0, chunk, self.vcode)
+        need = int(self.L.ame_mstep_work_size(ctypes.byref(dims)))
+        x, cov = self.x_a, self.cov
+        with torch.cuda.device(self.dev):
+            wk = getattr(self, "_mstep_work", None)
+            if wk is None or wk.numel() < need:
+                wk = self._mstep_work = torch.empty(need, dtype=torch.float64, device=self.dev)
+            state = torch.empty(TL, 2, d, d, dtype=torch.float64, device=self.dev)
+            dyad = torch.empty(TL, 4, dtype=torch.float64, device=self.dev)
+        st = self._elbo_stream_begin()
+        sp = ctypes.c_void_p(st.cuda_stream)
+        tok = self._tic("mstep", st)
+        for s0 in range(0, TL, chunk):
+            s1 = min(TL, s0 + chunk)
+            dm = _lib.ame_dims(n, self.r, s1 - s0, sh.t_begin + s0, sh.T_total, self.vcode)
+            a = _lib.ame_mstep_args(
+                x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]),
+                prev_final=prev_final if s0 == 0 else _ptr(x[s0 - 1]),
+                Yt=_ptr(self.Yt[s0:s1]), state=_ptr(state[s0:s1]), dyad=_ptr(dyad[s0:s1]),
+                work=_ptr(wk))
+            _lib.check(self.L.ame_mstep_stats(ctypes.byref(dm), ctypes.byref(a), sp),
+                       "ame_mstep_stats")
+        self._toc(tok)
+        self._elbo_stream_end(st)
+        return state, dyad
+
+    def set_constants(self, model):
+        """Rebuild the fp64 constants from the model's (updated) fp32 attributes,
+        exactly as at construction, and copy them into the device tensors the
+        kernels already point to, ordered after any dropped speculative sweep."""
+        self.discard_speculation()
+        self.C = Constants(model)
+        self.consts.copy_(self.C.stack)
+        self.phi.copy_(self.C.Phi.contiguous())
+        self._mark_host_writes()
+        self.invalidate()
+
     def forecast_states(self, m_last: torch.Tensor, S_last: torch.Tensor, n_steps: int):
         """h-step forecast of the states from the last fitted slice: m_k = Phi
         m_{k-1}, S_k = Phi S_{k-1} Phi' + Q, batched over nodes in fp64 on the

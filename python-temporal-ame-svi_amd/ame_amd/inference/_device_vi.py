@@ -327,6 +327,81 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         eng, (m, S) = self._forecast_states(n_steps)
         return self._dense(eng, m, S, rows, cols, include_noise, max_elements)
 
+    # ---------------- variational EM: learn Phi, Q, R, Sigma, Psi (extension) ----------------
+    # The reference never estimates the model parameters.  The E-step is the
+    # sweep; the M-step is closed-form (ame_amd/mstep.py) given sufficient
+    # statistics of q that the device computes (ame_mstep_stats).  q is
+    # mean-field across time, so posterior variances are underestimated and the
+    # estimates of Q and R are biased; at small n the Phi of the multiplicative
+    # block is poorly identified (U V' is rotation-invariant): update=("R", "Q")
+    # or phi_structure="scalar" restrict the step.
+    def m_step_statistics(self) -> dict:
+        """fp64 CPU tensors ``A0, A11, A00, A10`` (d, d), ``Rss`` (2, 2) and the
+        pair count ``pairs`` of the current q.  Time-sharded: a collective; every
+        rank adds all T slices in time order and returns the same bits."""
+        from .. import mstep
+        eng = self._predict_engine()
+        state, dyad = eng.mstep_stats()
+        if getattr(self, "_halo", None) is not None:
+            state = self._halo.gather_time(state.unsqueeze(0), 1)[0]
+            dyad = self._halo.gather_time(dyad.unsqueeze(0), 1)[0]
+        return mstep.combine(state, dyad)
+
+    def _model_params64(self) -> dict:
+        m = self.model
+        return {k: getattr(m, k).detach().to("cpu", torch.float64).clone()
+                for k in ("Phi", "Q", "R", "Sigma", "Psi")}
+
+    def m_step(self, update=("Phi", "Q", "R", "Sigma0"), phi_structure="full", apply=True) -> dict:
+        """One closed-form M-step on the current q.  Returns the new fp64 ``Phi,
+        Q, R, Sigma, Psi`` (those not in ``update`` unchanged) with
+        ``objective_before`` / ``objective_after``: the expected complete-data
+        log-likelihood F (ame_amd/mstep.py) at the model's parameters and at the
+        returned ones, and ``objective_scale``, the sum of the |terms| of F (its
+        evaluation error is a small multiple of 2^-52 of that).  ``apply`` writes them to the model as fp32 (``R_inv``
+        with ``R``) and rebuilds the engine's constants from those attributes,
+        as a fresh VI on the updated model would.  A non-finite or
+        non-positive-definite result raises ValueError and applies nothing."""
+        from .. import mstep
+        stats = self.m_step_statistics()
+        old = self._model_params64()
+        new = mstep.solve(stats, old, self.n, self.T, update, phi_structure)
+        new32 = {k: v.to(torch.float32) for k, v in new.items()}
+        mstep.validate(new)
+        mstep.validate({k: v.double() for k, v in new32.items()})
+        out = dict(new)
+        out["objective_before"] = mstep.objective(stats, old, self.n, self.T)
+        out["objective_after"] = mstep.objective(stats, new, self.n, self.T)
+        out["objective_scale"] = mstep.objective_scale(stats, new, self.n, self.T)
+        if apply:
+            m = self.model
+            changed = {"Phi": ("Phi",), "Q": ("Q",), "R": ("R",), "Sigma0": ("Sigma", "Psi")}
+            for u in update:
+                for k in changed[u]:
+                    setattr(m, k, new32[k])
+            if "R" in update:
+                m.R_inv = torch.linalg.inv(m.R)
+            self._ensure_engine().set_constants(m)
+        return out
+
+    def fit_em(self, n_rounds: int = 10, inner_iter: int = 10,
+               update=("Phi", "Q", "R", "Sigma0"), phi_structure="full",
+               tolerance: float = 1e-4, verbose: bool = True):
+        """Variational EM: ``n_rounds`` rounds of ``fit(max_iter=inner_iter)``
+        followed by ``m_step(update, phi_structure)``.  ``history["em"]`` gains
+        one m_step dictionary per round; ``history["elbo"]`` and
+        ``history["reconstruction_error"]`` keep growing as repeated fit() calls
+        make them."""
+        em = self.history.setdefault("em", [])
+        for k in range(int(n_rounds)):
+            self.fit(max_iter=inner_iter, tolerance=tolerance, verbose=False)
+            res = self.m_step(update=update, phi_structure=phi_structure, apply=True)
+            em.append(res)
+            if verbose:
+                print(f"EM round {k:3d} | F: {res['objective_before']:.4f} -> "
+                      f"{res['objective_after']:.4f} | ELBO: {float(self.history['elbo'][-1]):10.2f}")
+        return self.history
+
     def get_variational_means(self) -> torch.Tensor:
         return self.X_mean
 

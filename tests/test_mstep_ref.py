@@ -1,0 +1,223 @@
+"""The M-step reference (tests/mstep_ref.py) against its own definition, and
+the package's host algebra (ame_amd/mstep.py) against the reference.  No GPU.
+
+Each closed form must maximise F = mstep_ref.objective over its own block:
+the numerical gradient vanishes there and no perturbation raises F.  F is
+strictly concave in each precision matrix and quadratic in Phi, so a central
+difference of step h has error O(h^2 |F'''|); the gradient is compared with the
+gradient at a point displaced by 10 % of the parameter (which is far from zero)
+rather than with an absolute number.
+"""
+import numpy as np
+import pytest
+
+import mstep_ref as M
+import predictive_ref as PR
+
+SHAPES = ((12, 4, 2), (9, 3, 1), (20, 2, 3))
+
+
+def _case(shape, seed=0):
+    n, T, r = shape
+    X, S = PR.make_state(n, T, r, seed)
+    rng = np.random.default_rng(17 + seed)
+    Y = rng.standard_normal((n, n, T, 2))
+    st = M.statistics(X, S, r, Y)
+    d = 2 + 2 * r
+    A = rng.standard_normal((d, d)) / np.sqrt(d)
+    B = rng.standard_normal((2, 2))
+    p = dict(Phi=0.6 * np.eye(d) + 0.1 * A, Q=0.2 * np.eye(d) + 0.1 * A @ A.T,
+             R=0.3 * np.eye(2) + 0.1 * B @ B.T, Sigma=np.array([[1.0, 0.4], [0.4, 1.2]]),
+             Psi=np.eye(2 * r) + 0.2 * A[2:, 2:] @ A[2:, 2:].T)
+    return n, T, r, st, p, rng
+
+
+def _num_grad(f, x, h=1e-5):
+    g = np.zeros_like(x)
+    for idx in np.ndindex(*x.shape):
+        e = np.zeros_like(x)
+        e[idx] = h
+        g[idx] = (f(x + e) - f(x - e)) / (2 * h)
+    return g
+
+
+def _sym_dirs(rng, k, count):
+    for _ in range(count):
+        a = rng.standard_normal((k, k))
+        yield 0.5 * (a + a.T)
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_closed_forms_are_stationary_and_maximal(shape):
+    n, T, r, st, p, rng = _case(shape)
+    new = M.m_step(st, p, n, T)
+    f_new = M.objective(st, new, n, T)
+    assert f_new >= M.objective(st, p, n, T)
+
+    def with_(key, val):
+        return M.objective(st, dict(new, **{key: val}), n, T)
+
+    # Phi: unconstrained; gradient over all entries
+    g = _num_grad(lambda x: with_("Phi", x), new["Phi"])
+    g_off = _num_grad(lambda x: with_("Phi", x), 1.1 * new["Phi"])
+    print(f"Phi: |grad| at the maximiser {np.abs(g).max():.3e}, displaced {np.abs(g_off).max():.3e}")
+    assert np.abs(g).max() <= 1e-6 * np.abs(g_off).max()
+    for _ in range(20):
+        dPhi = rng.standard_normal(new["Phi"].shape)
+        for eps in (1e-3, 1e-1):
+            assert with_("Phi", new["Phi"] + eps * dPhi) <= f_new
+    # Q, R: symmetric positive definite; gradient along symmetric directions
+    for key in ("Q", "R"):
+        k = new[key].shape[0]
+        scale = np.abs(new[key]).max()
+        for D in _sym_dirs(rng, k, 10):
+            f = lambda s, base=new[key]: with_(key, base + s * scale * D)
+            slope = (f(1e-5) - f(-1e-5)) / 2e-5
+            f_off = lambda s, base=1.1 * new[key]: with_(key, base + s * scale * D)
+            slope_off = (f_off(1e-5) - f_off(-1e-5)) / 2e-5
+            assert abs(slope) <= 1e-5 * max(abs(slope_off), 1.0), (key, slope, slope_off)
+            for eps in (1e-3, 5e-2):
+                cand = new[key] + eps * scale * D
+                if np.linalg.eigvalsh(cand).min() > 0:
+                    assert with_(key, cand) <= f_new, (key, eps)
+    # Sigma, Psi: the block-diagonal S0
+    for key in ("Sigma", "Psi"):
+        k = new[key].shape[0]
+        scale = np.abs(new[key]).max()
+        for D in _sym_dirs(rng, k, 10):
+            f = lambda s: with_(key, new[key] + s * scale * D)
+            slope = (f(1e-5) - f(-1e-5)) / 2e-5
+            f_off = lambda s: with_(key, 1.1 * new[key] + s * scale * D)
+            slope_off = (f_off(1e-5) - f_off(-1e-5)) / 2e-5
+            assert abs(slope) <= 1e-5 * max(abs(slope_off), 1.0), (key, slope, slope_off)
+            cand = new[key] + 1e-2 * scale * D
+            if np.linalg.eigvalsh(cand).min() > 0:
+                assert with_(key, cand) <= f_new, key
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_q_is_maximal_for_any_phi_and_subsets_leave_the_rest(shape):
+    n, T, r, st, p, rng = _case(shape, seed=1)
+    only_q = M.m_step(st, p, n, T, update=("Q",))
+    for k in ("Phi", "R", "Sigma", "Psi"):
+        assert np.array_equal(only_q[k], p[k])
+    f = M.objective(st, only_q, n, T)
+    assert f >= M.objective(st, p, n, T)
+    for D in _sym_dirs(rng, only_q["Q"].shape[0], 20):
+        cand = only_q["Q"] + 1e-3 * np.abs(only_q["Q"]).max() * D
+        if np.linalg.eigvalsh(cand).min() > 0:
+            assert M.objective(st, dict(only_q, Q=cand), n, T) <= f
+    only_r = M.m_step(st, p, n, T, update=("R",))
+    for k in ("Phi", "Q", "Sigma", "Psi"):
+        assert np.array_equal(only_r[k], p[k])
+    assert not np.array_equal(only_r["R"], p["R"])
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_scalar_phi_step_does_not_lower_F(shape):
+    n, T, r, st, p, rng = _case(shape, seed=2)
+    d = 2 + 2 * r
+    p = dict(p, Phi=0.4 * np.eye(d))
+    f0 = M.objective(st, p, n, T)
+    # the conditional step: phi given the old Q is the maximiser over phi ...
+    phi = M.phi_scalar(st, p["Q"])
+    f_phi = M.objective(st, dict(p, Phi=phi * np.eye(d)), n, T)
+    assert f_phi >= f0
+    for dphi in (-0.1, -1e-3, 1e-3, 0.1):
+        assert M.objective(st, dict(p, Phi=(phi + dphi) * np.eye(d)), n, T) <= f_phi
+    # ... and Q given that phi does not lower it again
+    new = M.m_step(st, p, n, T, update=("Phi", "Q"), phi_structure="scalar")
+    assert np.array_equal(new["Phi"], phi * np.eye(d))
+    assert M.objective(st, new, n, T) >= f_phi
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_rss_diagonal_is_sq_err_plus_mean_var(shape):
+    """Rss00 and Rss11 of a slice equal sums[7] + sums[5] and sums[8] + sums[6]
+    of the predictive reference scored with zero noise."""
+    n, T, r, st, p, rng = _case(shape)
+    X, S = PR.make_state(n, T, r, 0)
+    Y = np.random.default_rng(17).standard_normal((n, n, T, 2))
+    rows, _ = M.dyad_rows(X, S, r, Y)
+    zsq, csq = PR.thresholds(())
+    for t in range(T):
+        sums, _ = PR.score_slice(X[:, t], S[:, t], r, Y[:, :, t], np.zeros((2, 2)), zsq, csq)
+        assert rows[t, 0] == sums[0] == n * (n - 1) // 2
+        assert abs(rows[t, 1] - (sums[7] + sums[5])) <= 1e-12 * abs(rows[t, 1])
+        assert abs(rows[t, 2] - (sums[8] + sums[6])) <= 1e-12 * abs(rows[t, 2])
+    assert abs(st["Rss"][0, 0] - rows[:, 1].sum()) <= 1e-12 * st["Rss"][0, 0]
+    assert st["Rss"][0, 1] == st["Rss"][1, 0]
+
+
+def test_statistics_definitions():
+    """A0, A11, A00, A10 against the plain double loop of their definition."""
+    n, T, r = 7, 4, 2
+    X, S = PR.make_state(n, T, r, 3)
+    st = M.statistics(X, S, r, np.zeros((n, n, T, 2)))
+    X64, S64 = X.astype(np.float64), S.astype(np.float64)
+    d = 2 + 2 * r
+    A0, A11, A00, A10 = (np.zeros((d, d)) for _ in range(4))
+    for i in range(n):
+        A0 += np.outer(X64[i, 0], X64[i, 0]) + S64[i, 0]
+        for t in range(1, T):
+            A11 += np.outer(X64[i, t], X64[i, t]) + S64[i, t]
+            A00 += np.outer(X64[i, t - 1], X64[i, t - 1]) + S64[i, t - 1]
+            A10 += np.outer(X64[i, t], X64[i, t - 1])
+    for k, want in (("A0", A0), ("A11", A11), ("A00", A00), ("A10", A10)):
+        assert np.abs(st[k] - want).max() <= 1e-12 * np.abs(want).max(), k
+    assert st["pairs"] == T * n * (n - 1) // 2
+
+
+@pytest.mark.parametrize("phi_structure", ["full", "scalar"])
+def test_package_algebra_matches_reference(phi_structure):
+    """ame_amd.mstep (torch, fp64) against the numpy reference: combine, solve,
+    objective; validate() refuses non-finite and indefinite results."""
+    import torch
+    from ame_amd import mstep
+    n, T, r, st, p, rng = _case((12, 4, 2))
+    X, S = PR.make_state(n, T, r, 0)
+    Y = np.random.default_rng(17).standard_normal((n, n, T, 2))
+    srows, _ = M.state_rows(X, S)
+    drows, _ = M.dyad_rows(X, S, r, Y)
+    got = mstep.combine(torch.from_numpy(srows), torch.from_numpy(drows))
+    for k in ("A0", "A11", "A00", "A10", "Rss"):
+        assert np.abs(got[k].numpy() - st[k]).max() <= 1e-13 * np.abs(st[k]).max(), k
+    assert got["pairs"] == st["pairs"]
+    tp = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in p.items()}
+    for update in (("Phi", "Q", "R", "Sigma0"), ("R", "Q"), ("Phi",)):
+        want = M.m_step(st, p, n, T, update, phi_structure)
+        new = mstep.solve(got, tp, n, T, update, phi_structure)
+        for k in M.PARAMS:
+            assert np.abs(new[k].numpy() - want[k]).max() <= 1e-11 * np.abs(want[k]).max(), (update, k)
+        mstep.validate(new)
+        f_ref = M.objective(st, want, n, T)
+        assert abs(mstep.objective(got, new, n, T) - f_ref) <= 1e-11 * M.objective_magnitude(st, want, n, T)
+    with pytest.raises(ValueError):
+        mstep.solve(got, tp, n, T, ("Phi", "S"))
+    with pytest.raises(ValueError):
+        mstep.solve(got, tp, n, T, ("Phi",), "diagonal")
+    with pytest.raises(ValueError):
+        mstep.validate(dict(tp, R=torch.tensor([[1.0, 2.0], [2.0, 1.0]], dtype=torch.float64)))
+    with pytest.raises(ValueError):
+        mstep.validate(dict(tp, Q=tp["Q"] * float("nan")))
+
+
+def test_oracle_em_recovers_the_parameters_and_fp32_sensitivity():
+    """The CPU experiment the GPU end-to-end test repeats (n = 40, T = 16, r = 2,
+    seed 3, start ar = 0.5 and 3 R): F never decreases within a round, the
+    estimates approach the truth, and the same EM on fp32 state arrays differs
+    from the fp64 run by the reference's own fp32 sensitivity (printed; the GPU
+    test allows 4 x the round-1 figure)."""
+    import em_case
+    c = em_case.cpu_runs()
+    a, b = c["em64"], c["em32"]
+    for k, rd in enumerate(a):
+        slack = 2.0 ** -40 * abs(rd["objective_before"])
+        assert rd["objective_after"] >= rd["objective_before"] - slack, k
+    last = a[-1]
+    print("Phi diag (additive):", np.diag(last["Phi"])[:2], "R:", last["R"].ravel()[[0, 1, 3]])
+    assert np.abs(np.diag(last["Phi"])[:2] - M.TRUE_AR).max() <= 0.1
+    assert np.abs(last["R"].ravel()[[0, 1, 3]] - np.array(M.TRUE_R)).max() <= 0.05
+    dev = em_case.relative_deviation(a[0], b[0])
+    print(f"round-1 fp32 sensitivity (max over Phi, Q, R of max|d| / max|param|): {dev:.3e}")
+    assert 0.0 < dev < 1e-5
