@@ -32,6 +32,10 @@
  *   ame_mstep_stats   replaces nothing in the reference: the sufficient
  *                     statistics of q from which the closed-form M-step of
  *                     variational EM re-estimates Phi, Q, R, Sigma and Psi.
+ *   ame_smooth        replaces nothing in the reference: each node's exact
+ *                     Gaussian posterior across time given the other nodes'
+ *                     means (block-tridiagonal solve): smoothed means, marginal
+ *                     covariances and lag-one cross-covariances.
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -384,6 +388,72 @@ int ame_mstep_stats(const ame_dims* dims, const ame_mstep_args* args, void* stre
 /* Scratch doubles ame_mstep_stats needs (chunk partials, feature rows, tile
  * partials), -1 on bad dims. */
 long long ame_mstep_work_size(const ame_dims* dims);
+
+/* ---- exact per-node smoothing across time --------------------------------------
+ * Replaces nothing the reference computes.  The sweep leaves a posterior that is
+ * mean-field across nodes AND time: each covariance is the inverse of one
+ * diagonal block of a node's precision.  Given the current means of the other
+ * nodes, node i's exact Gaussian posterior over its whole trajectory has the
+ * block-tridiagonal precision
+ *   D_t = P_obs(i,t) + [t = 0] S0inv + [t > 0] Qinv + [t < T-1] PtQiP      (d x d)
+ *   O   = -QiPhi                   block (t, t-1), t >= 1; O' is block (t-1, t)
+ *   h_t = h_obs(i,t) = sum_{j != i} J_j' R_inv y_ij
+ *   Lambda_i = blocktridiag(D, O),  mu_i = Lambda_i^-1 h,  S_i = Lambda_i^-1
+ * with P_obs, h_obs as the sweep builds them (structured_mf.py:289-326) from
+ * the means `x`.  ame_smooth returns, for the nodes [i0, i1), the means mu_it,
+ * the marginals S_i[t,t] and the lag-one blocks X_it = S_i[t,t-1] (X_i0 = 0).
+ * Three differences from the sweep's per-step inverse:
+ *   - no 1e-6 jitter is added;
+ *   - no "bad" masking and no naive diagonal: the smoother is the same for every
+ *     variant (dims.variant is only range-checked, as in ame_predict);
+ *   - P_obs is built from the symmetric part of R_inv, so Lambda_i is symmetric
+ *     for an asymmetric R_inv too; h_obs keeps R_inv as given.
+ * Lambda_i is positive definite whenever S0 and Q are: the factorisation does
+ * not pivot.  Time sharding is not supported: t_begin = 0 and T_local = T_total.
+ *
+ * Two stages (kernels in csrc/ame_smooth.hip), all sums and products fp64:
+ * the observation stage (per-slice Gram statistics of (U, V) and h_obs, one pass
+ * over the rows [i0, i1) of Yt) and the solve stage (one workgroup per node, a
+ * forward and a backward pass over t; the per-step factors live in `work`).
+ * mean / cov / cross are rounded to fp32 once.  lag_sum[t] = sum_i X_it is added
+ * from the fp64 values in fixed chunks of 32 nodes, chunk by chunk in node
+ * order: a call with i0 = 0 starts it from zero, a call with i0 > 0 continues
+ * it, so calls over consecutive node ranges (i0 a multiple of 32, in ascending
+ * order on one stream) give the same bits as one call over all nodes.
+ * No atomics in the sums and no waits between workgroups.
+ *
+ * Failure: a non-positive (or NaN) pivot does not fault; that node's outputs
+ * (and lag_sum) become NaN and `fail` records it: [0] nodes that failed, [1]
+ * claim word, [2] node and [3] slice of the first to report.  The caller zeroes
+ * `fail` and reads it after the stream has finished. */
+#define AME_SMOOTH_STAGE_OBS 1
+#define AME_SMOOTH_STAGE_SOLVE 2
+#define AME_SMOOTH_FAIL_WORDS 4
+typedef struct ame_smooth_args {
+    const float* x;          /* [T][n][d] means of ALL nodes (conditioning values) */
+    const float* Yt;         /* [T][n][ny][2] packed observations (ame_pack_y) */
+    const double* consts;    /* fp64 [5][d][d] */
+    double rinv[4];          /* R_inv row-major, exactly as the sweep receives it */
+    int32_t i0, i1;          /* nodes [i0, i1) of this call; i0 a multiple of 32 */
+    int32_t stages;          /* 0 = both; AME_SMOOTH_STAGE_* bits run one stage alone (timing:
+                                the solve stage then reads what an observation stage of the
+                                same dims and node range left in `work`) */
+    float* mean;             /* [T][n][d]    rows [i0, i1) of every slice are written */
+    float* cov;              /* [T][n][d][d] */
+    float* cross;            /* [T][n][d][d] X_it = S_i[t,t-1]; slice 0 is zero */
+    double* lag_sum;         /* [T][d][d] fp64 */
+    uint32_t* fail;          /* [AME_SMOOTH_FAIL_WORDS] */
+    double* work;            /* >= ame_smooth_work_size(dims, i1 - i0) doubles */
+    uint64_t work_doubles;   /* size of `work` in doubles, checked */
+} ame_smooth_args;
+int ame_smooth(const ame_dims* dims, const ame_smooth_args* args, void* stream);
+/* Scratch doubles one ame_smooth call over `nodes` nodes needs: T (1+2r)^2 Gram
+ * statistics + nodes T (d^2 + 2d) (h_obs, J_t^-1 g_t, J_t^-1); -1 on bad
+ * dims or nodes outside [1, n]. */
+long long ame_smooth_work_size(const ame_dims* dims, int nodes);
+/* Dynamic LDS bytes of the solve workgroup at latent dim r (four d x (d+1) fp64
+ * matrices and six d-vectors), -1 for an r that is not compiled in. */
+long long ame_smooth_lds_bytes(int r);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

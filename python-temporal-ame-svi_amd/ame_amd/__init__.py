@@ -9,6 +9,8 @@ from .models import TemporalAMEModel
 from .inference import (BaseTemporalVariationalInference, BaseVariationalInference,
                         TemporalAMENaiveMFVI, TemporalAMEStructuredMFVI)
 
-__all__ = ["TemporalAMEModel", "TemporalAMEStructuredMFVI", "TemporalAMENaiveMFVI",
+from .inference._device_vi import SmoothResult
+
+__all__ = ["SmoothResult", "TemporalAMEModel", "TemporalAMEStructuredMFVI", "TemporalAMENaiveMFVI",
            "BaseVariationalInference", "BaseTemporalVariationalInference"]
 __version__ = "0.1.0"

@@ -31,6 +31,9 @@ long long ame_mstep_state_blocks(const ame_dims*);
 int ame_mstep_dyad_dispatch(const ame_dims*, const ame_mstep_args*, double* work, hipStream_t);
 long long ame_mstep_dyad_work_doubles(const ame_dims*);
 long long ame_mstep_dyad_blocks(const ame_dims*);
+int ame_smooth_dispatch(const ame_dims*, const ame_smooth_args*, hipStream_t);
+long long ame_smooth_work_doubles(const ame_dims*, int nodes);
+long long ame_smooth_lds_bytes_r(int r);
 int ame_pack_dispatch(const float*, float*, const ame_dims*, unsigned long long*, hipStream_t);
 
 static thread_local char g_err[512] = "";
@@ -476,6 +479,42 @@ int ame_mstep_stats(const ame_dims* dims, const ame_mstep_args* a, void* stream)
         return launched(ame_mstep_dyad_dispatch(dims, a, a->work + ame_mstep_state_work_doubles(dims),
                                                 (hipStream_t)stream), "mstep_dyad");
     return 0;
+}
+
+long long ame_smooth_work_size(const ame_dims* dims, int nodes) {
+    if (check_dims(dims)) return -1;
+    if (nodes < 1 || nodes > dims->n) return fail("ame_smooth_work_size: nodes=%d outside [1, n]", nodes);
+    return ame_smooth_work_doubles(dims, nodes);
+}
+
+long long ame_smooth_lds_bytes(int r) {
+    if (!r_supported(r)) return fail("ame_smooth_lds_bytes: latent_dim r=%d not compiled into this library", r);
+    return ame_smooth_lds_bytes_r(r);
+}
+
+int ame_smooth(const ame_dims* dims, const ame_smooth_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_smooth: args is NULL");
+    if (dims->t_begin != 0 || dims->T_local != dims->T_total)
+        return fail("ame_smooth: needs every slice on this rank (t_begin=%d, T_local=%d): time "
+                    "sharding is not supported", dims->t_begin, dims->T_local);
+    if (!a->x || !a->Yt || !a->consts || !a->work)
+        return fail("ame_smooth: NULL input buffer (x, Yt, consts, work)");
+    if (!a->mean || !a->cov || !a->cross || !a->lag_sum || !a->fail)
+        return fail("ame_smooth: NULL output buffer (mean, cov, cross, lag_sum, fail)");
+    if (a->i0 < 0 || a->i0 >= a->i1 || a->i1 > dims->n)
+        return fail("ame_smooth: nodes [%d, %d) outside [0, n]", a->i0, a->i1);
+    if (a->i0 % 32 != 0) return fail("ame_smooth: i0=%d is not a multiple of 32", a->i0);
+    if (a->stages < 0 || a->stages > (AME_SMOOTH_STAGE_OBS | AME_SMOOTH_STAGE_SOLVE))
+        return fail("ame_smooth: bad stages %d", a->stages);
+    const long long need = ame_smooth_work_doubles(dims, a->i1 - a->i0);
+    if ((long long)a->work_doubles < need)
+        return fail("ame_smooth: work holds fewer doubles than ame_smooth_work_size (%d nodes)",
+                    a->i1 - a->i0);
+    if ((long long)dims->T_local * ((a->i1 - a->i0 + 31) / 32) > 0x7FFFFFFFLL)
+        return fail("ame_smooth: T_local=%d slices of %d nodes exceed one launch; pass fewer nodes",
+                    dims->T_local, a->i1 - a->i0);
+    return launched(ame_smooth_dispatch(dims, a, (hipStream_t)stream), "smooth");
 }
 
 static int check_align(int n, int T, int r) {

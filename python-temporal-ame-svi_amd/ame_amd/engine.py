@@ -889,8 +889,9 @@ class DeviceEngine:
     # ------------------------------------------------------------------
     # M-step sufficient statistics and new constants (ame_mstep_stats)
     # ------------------------------------------------------------------
-    def mstep_stats(self):
-        """Per-slice sufficient statistics of the current state for the M-step:
+    def mstep_stats(self, x=None, cov=None):
+        """Per-slice sufficient statistics of the current state (or of the given
+        [T_local][n][d] means and [T_local][n][d][d] covariances) for the M-step:
         ``state`` [T_local][2][d][d] (P_t, C_t) and ``dyad`` [T_local][4] (pairs,
         Rss00, Rss11, Rss01), fp64 on the device.  Whole slices at a time within
         the scratch budget of predict(); a slice's row does not depend on the
@@ -906,7 +907,8 @@ class DeviceEngine:
         chunk = max(1, min(TL, self.PREDICT_WORK_DOUBLES // per))
         dims = _lib.ame_dims(n, self.r, chunk, 0, chunk, self.vcode)
         need = int(self.L.ame_mstep_work_size(ctypes.byref(dims)))
-        x, cov = self.x_a, self.cov
+        if x is None:
+            x, cov = self.x_a, self.cov
         with torch.cuda.device(self.dev):
             wk = getattr(self, "_mstep_work", None)
             if wk is None or wk.numel() < need:
@@ -929,6 +931,68 @@ class DeviceEngine:
         self._toc(tok)
         self._elbo_stream_end(st)
         return state, dyad
+
+    # ------------------------------------------------------------------
+    # exact per-node smoothing across time (ame_smooth)
+    # ------------------------------------------------------------------
+    def smooth_chunk(self):
+        """Nodes per ame_smooth call within the scratch budget of predict(): all n,
+        or a multiple of 32 (at least 32)."""
+        n = self.n
+        w1 = int(self.L.ame_smooth_work_size(ctypes.byref(self.dims), 1))
+        w2 = int(self.L.ame_smooth_work_size(ctypes.byref(self.dims), 2)) if n >= 2 else -1
+        if w1 < 0 or w2 < 0:
+            _lib.check(-1, "ame_smooth_work_size")
+        per, base = w2 - w1, 2 * w1 - w2
+        fit = (self.PREDICT_WORK_DOUBLES - base) // per
+        return n if fit >= n else min(n, max(32, fit // 32 * 32))
+
+    def smooth(self, stages=0, check=True):
+        """Each node's exact Gaussian posterior across time given the current
+        means of the others (include/ame_amd.h, ame_smooth): new device tensors
+        ``mean`` [T][n][d], ``cov`` and ``cross`` [T][n][d][d] (fp32) and
+        ``lag_sum`` [T][d][d] (fp64).  Reads x_a, Yt, consts and rinv; writes
+        nothing the sweep reads.  Nodes go in chunks (multiples of 32) within
+        the scratch budget of predict(); the result has the same bits for any
+        chunking.  A node whose factorisation met a non-positive pivot raises
+        RuntimeError (its outputs are NaN).  Runs on the ELBO stream."""
+        if self.halo is not None or self.shard.T_local != self.shard.T_total:
+            raise NotImplementedError("smooth is not available on a time-sharded run")
+        self.discard_speculation()
+        n, d, T = self.n, self.d, self.shard.T_local
+        chunk = self.smooth_chunk()
+        need = int(self.L.ame_smooth_work_size(ctypes.byref(self.dims), chunk))
+        x = self.x_a
+        with torch.cuda.device(self.dev):
+            wk = getattr(self, "_smooth_work", None)
+            if wk is None or wk.numel() < need:
+                wk = self._smooth_work = torch.empty(need, dtype=torch.float64, device=self.dev)
+            mean = torch.empty(T, n, d, dtype=torch.float32, device=self.dev)
+            cov = torch.empty(T, n, d, d, dtype=torch.float32, device=self.dev)
+            cross = torch.empty(T, n, d, d, dtype=torch.float32, device=self.dev)
+            lag = torch.empty(T, d, d, dtype=torch.float64, device=self.dev)
+            fail = torch.zeros(_lib.AME_SMOOTH_FAIL_WORDS, dtype=torch.int32, device=self.dev)
+        st = self._elbo_stream_begin()
+        sp = ctypes.c_void_p(st.cuda_stream)
+        tok = self._tic("smooth", st)
+        for i0 in range(0, n, chunk):
+            a = _lib.ame_smooth_args(
+                x=_ptr(x), Yt=_ptr(self.Yt), consts=_ptr(self.consts), rinv=self.C.rinv4(),
+                i0=i0, i1=min(n, i0 + chunk), stages=int(stages), mean=_ptr(mean), cov=_ptr(cov),
+                cross=_ptr(cross), lag_sum=_ptr(lag), fail=_ptr(fail), work=_ptr(wk),
+                work_doubles=wk.numel())
+            _lib.check(self.L.ame_smooth(ctypes.byref(self.dims), ctypes.byref(a), sp), "ame_smooth")
+        self._toc(tok)
+        self._elbo_stream_end(st)
+        for t in (x, self.Yt, self.consts, wk, mean, cov, cross, lag, fail):
+            t.record_stream(st)
+        if check:
+            words = [int(w) & 0xFFFFFFFF for w in fail.cpu().tolist()]
+            if words[0]:
+                raise RuntimeError(f"ame_amd: smooth met a non-positive pivot at {words[0]} node(s); "
+                                   f"first reported: node {words[2]}, time {words[3]} (the "
+                                   "precision of that node's trajectory is not positive definite)")
+        return mean, cov, cross, lag
 
     def set_constants(self, model):
         """Rebuild the fp64 constants from the model's (updated) fp32 attributes,

@@ -36,6 +36,35 @@ def default_device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+class SmoothResult:
+    """What ``vi.smooth()`` returns: each node's exact Gaussian posterior across
+    time given the other nodes' means.  Holds the device tensors (time-major,
+    ``d_mean`` [T][n][d], ``d_cov`` / ``d_cross`` [T][n][d][d] fp32, ``d_lag_sum``
+    [T][d][d] fp64) and hands out CPU copies in the reference's layout:
+    ``mean`` (n, T, d), ``cov`` (n, T, d, d), ``cross`` (n, T, d, d) with
+    cross[i, t] = Cov(x_it, x_i,t-1) (zero at t = 0) and ``lag_sum`` (T, d, d)
+    = sum_i cross[i, t] in fp64."""
+
+    def __init__(self, mean, cov, cross, lag_sum):
+        self.d_mean, self.d_cov, self.d_cross, self.d_lag_sum = mean, cov, cross, lag_sum
+
+    @property
+    def mean(self):
+        return self.d_mean.permute(1, 0, 2).to("cpu").contiguous()
+
+    @property
+    def cov(self):
+        return self.d_cov.permute(1, 0, 2, 3).to("cpu").contiguous()
+
+    @property
+    def cross(self):
+        return self.d_cross.permute(1, 0, 2, 3).to("cpu").contiguous()
+
+    @property
+    def lag_sum(self):
+        return self.d_lag_sum.to("cpu")
+
+
 class DeviceTemporalVI(BaseTemporalVariationalInference):
     _variant = "good"
 
@@ -97,13 +126,26 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
             self._ver[key] is None or h._version != self._ver[key])
 
     # ---------------- engine lifecycle ----------------
-    def _make_halo(self):
+    def _time_sharded(self) -> bool:
+        """Whether this run is (or, before the engine exists, will be) time-sharded;
+        decided without a collective."""
+        if self._engine is not None:
+            return getattr(self, "_halo", None) is not None
+        return self._wants_halo()
+
+    def _wants_halo(self) -> bool:
         import torch.distributed as dist
         use = self._distributed
         if use is None:
             use = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        if not use:
+        return bool(use)
+
+    def _make_halo(self):
+        use = self._distributed
+        if not self._wants_halo():
             return None, None
+        if use is None:
+            use = True
         from ..distributed import TimeShardHalo
         # distributed=True / None: defaults; a dict: TimeShardHalo options (peer_mode)
         halo = TimeShardHalo.create(self.T, **(use if isinstance(use, dict) else {}))
@@ -256,17 +298,41 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         eng.discard_speculation()
         return eng
 
-    def predictive_check(self, levels=(0.5, 0.9, 0.95), include_noise=True) -> dict:
+    # ---------------- exact smoothing across time (extension) ----------------
+    def smooth(self) -> SmoothResult:
+        """Each node's exact Gaussian posterior over its whole trajectory given
+        the current means of the other nodes (ame_smooth): smoothed means, the
+        time-marginal covariances (never smaller than the fit's mean-field
+        blocks) and the lag-one cross-covariances.  Does not modify this object.
+        Not available on a time-sharded run."""
+        if self._time_sharded():
+            raise NotImplementedError("smooth is not available on a time-sharded run: the forward "
+                                      "pass would have to carry (J_t^-1, g_t) across ranks")
+        eng = self._predict_engine()
+        return SmoothResult(*eng.smooth())
+
+    def _state(self, smoothed):
+        """(engine, means, covariances, smoothing result or None) the extension
+        calls work from: the fit's state, or its smoothed counterpart."""
+        if smoothed:
+            sm = self.smooth()
+            return self._engine, sm.d_mean, sm.d_cov, sm
+        eng = self._predict_engine()
+        return eng, eng.x_a, eng.cov, None
+
+    def predictive_check(self, levels=(0.5, 0.9, 0.95), include_noise=True, smoothed=False) -> dict:
         """Score the observed network against the posterior-predictive moments of
         every dyad, in-sample.  fp64 arrays of length T: ``pairs``, ``log_score``
         (sum of log N(y_ij; E mu_ij, Sigma_ij) over pairs i < j), ``mahalanobis``,
         ``z2`` (T, 2), ``mean_var`` (T, 2), ``sq_err`` (T, 2), ``coverage``
         (T, L, 2) and ``joint_coverage`` (T, L) as fractions, and ``levels``.
         include_noise=False scores against the credible region of the mean.
-        Time-sharded: a collective, every rank returns all T steps."""
+        smoothed=True scores the smoothed means and covariances (:meth:`smooth`)
+        instead of the fit's.  Time-sharded: a collective, every rank returns all
+        T steps."""
         levels, zsq, csq = self._thresholds(levels)
-        eng = self._predict_engine()
-        sums, _ = eng.predict(eng.x_a, eng.cov, Yt=eng.Yt, include_noise=include_noise,
+        eng, x, cov, _ = self._state(smoothed)
+        sums, _ = eng.predict(x, cov, Yt=eng.Yt, include_noise=include_noise,
                               zsq=zsq, csq=csq)
         if getattr(self, "_halo", None) is not None:
             sums = self._halo.gather_time(sums.unsqueeze(0), 1)[0]
@@ -283,20 +349,25 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         dense = dense.permute(1, 2, 0, 3).to("cpu")
         return dense[..., :2].contiguous(), dense[..., 2:].contiguous()
 
-    def predict_dyads(self, times, rows=None, cols=None, include_noise=True, max_elements=2 ** 27):
+    def predict_dyads(self, times, rows=None, cols=None, include_noise=True, max_elements=2 ** 27,
+                      smoothed=False):
         """Dense predictive moments ``(mean, second)`` on the CPU: (ni, nj, S, 2)
         = E[mu_ij] and (ni, nj, S, 3) = Var of entry 0, Var of entry 1 and their
         covariance (with model.R added when include_noise).  ``times`` is an int
         or a slice, ``rows`` / ``cols`` contiguous ranges or slices.  The diagonal
-        holds compute_mean's means and NaN second moments."""
-        eng = self._predict_engine()
+        holds compute_mean's means and NaN second moments.  smoothed=True: of the
+        smoothed state (:meth:`smooth`)."""
+        eng, x, cov, _ = self._state(smoothed)
         if getattr(self, "_halo", None) is not None:
             raise NotImplementedError("predict_dyads is not available on a time-sharded run: "
                                       "score with predictive_check, or fit on one process")
         t0, t1 = self._range(times, self.T, "times")
-        return self._dense(eng, eng.x_a[t0:t1], eng.cov[t0:t1], rows, cols, include_noise, max_elements)
+        return self._dense(eng, x[t0:t1], cov[t0:t1], rows, cols, include_noise, max_elements)
 
-    def _forecast_states(self, n_steps):
+    def _forecast_states(self, n_steps, smoothed=False):
+        if smoothed:   # the smoothed last slice is the filtered one
+            eng, x, cov, _ = self._state(True)
+            return eng, eng.forecast_states(x[-1], cov[-1], n_steps)
         eng = self._predict_engine()
         if getattr(self, "_halo", None) is None:
             m, S = eng.x_a[-1], eng.cov[-1]
@@ -304,27 +375,31 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
             m, S = self.X_mean[:, -1], self.X_cov[:, -1]
         return eng, eng.forecast_states(m, S, n_steps)
 
-    def forecast(self, n_steps: int = 1):
+    def forecast(self, n_steps: int = 1, smoothed=False):
         """h-step forecast of the states from the last fitted slice, ``(X_pred
         (n, h, d), S_pred (n, h, d, d))`` on the CPU: m_k = Phi m_{k-1}, S_k = Phi
-        S_{k-1} Phi' + Q (the means are naive_mf.py:386-396's predict_forward)."""
-        _, (m, S) = self._forecast_states(n_steps)
+        S_{k-1} Phi' + Q (the means are naive_mf.py:386-396's predict_forward).
+        smoothed=True starts from the smoothed last slice (:meth:`smooth`), which
+        is the filtered one."""
+        _, (m, S) = self._forecast_states(n_steps, smoothed)
         return m.permute(1, 0, 2).to("cpu").contiguous(), S.permute(1, 0, 2, 3).to("cpu").contiguous()
 
-    def forecast_check(self, Y_future, levels=(0.5, 0.9, 0.95), include_noise=True) -> dict:
+    def forecast_check(self, Y_future, levels=(0.5, 0.9, 0.95), include_noise=True,
+                       smoothed=False) -> dict:
         """predictive_check of held-out steps: ``Y_future`` (n, n, h, 2) scored
         against the h-step forecast; the same dictionary, of length h."""
         levels, zsq, csq = self._thresholds(levels)
         Y_future = torch.as_tensor(Y_future)
-        eng, (m, S) = self._forecast_states(int(Y_future.shape[2]) if Y_future.dim() == 4 else 1)
+        eng, (m, S) = self._forecast_states(int(Y_future.shape[2]) if Y_future.dim() == 4 else 1,
+                                            smoothed)
         Yt = eng.pack_future(Y_future)
         sums, _ = eng.predict(m, S, Yt=Yt, include_noise=include_noise, zsq=zsq, csq=csq)
         return self._check_dict(sums, levels)
 
     def forecast_dyads(self, n_steps: int = 1, rows=None, cols=None, include_noise=True,
-                       max_elements=2 ** 27):
+                       max_elements=2 ** 27, smoothed=False):
         """predict_dyads of the h-step forecast: (ni, nj, h, 2) and (ni, nj, h, 3)."""
-        eng, (m, S) = self._forecast_states(n_steps)
+        eng, (m, S) = self._forecast_states(n_steps, smoothed)
         return self._dense(eng, m, S, rows, cols, include_noise, max_elements)
 
     # ---------------- variational EM: learn Phi, Q, R, Sigma, Psi (extension) ----------------
@@ -335,11 +410,18 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
     # estimates of Q and R are biased; at small n the Phi of the multiplicative
     # block is poorly identified (U V' is rotation-invariant): update=("R", "Q")
     # or phi_structure="scalar" restrict the step.
-    def m_step_statistics(self) -> dict:
+    def m_step_statistics(self, smoothed=False) -> dict:
         """fp64 CPU tensors ``A0, A11, A00, A10`` (d, d), ``Rss`` (2, 2) and the
         pair count ``pairs`` of the current q.  Time-sharded: a collective; every
-        rank adds all T slices in time order and returns the same bits."""
+        rank adds all T slices in time order and returns the same bits.
+        smoothed=True: the statistics of the smoothed posterior (:meth:`smooth`):
+        its means and marginals in place of the fit's, and its lag-one
+        cross-covariances added into A10."""
         from .. import mstep
+        if smoothed:
+            eng, x, cov, sm = self._state(True)
+            state, dyad = eng.mstep_stats(x, cov)
+            return mstep.combine(state, dyad, cross=sm.d_lag_sum)
         eng = self._predict_engine()
         state, dyad = eng.mstep_stats()
         if getattr(self, "_halo", None) is not None:
@@ -352,7 +434,8 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         return {k: getattr(m, k).detach().to("cpu", torch.float64).clone()
                 for k in ("Phi", "Q", "R", "Sigma", "Psi")}
 
-    def m_step(self, update=("Phi", "Q", "R", "Sigma0"), phi_structure="full", apply=True) -> dict:
+    def m_step(self, update=("Phi", "Q", "R", "Sigma0"), phi_structure="full", apply=True,
+               smoothed=False) -> dict:
         """One closed-form M-step on the current q.  Returns the new fp64 ``Phi,
         Q, R, Sigma, Psi`` (those not in ``update`` unchanged) with
         ``objective_before`` / ``objective_after``: the expected complete-data
@@ -363,7 +446,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         as a fresh VI on the updated model would.  A non-finite or
         non-positive-definite result raises ValueError and applies nothing."""
         from .. import mstep
-        stats = self.m_step_statistics()
+        stats = self.m_step_statistics(smoothed=smoothed)
         old = self._model_params64()
         new = mstep.solve(stats, old, self.n, self.T, update, phi_structure)
         new32 = {k: v.to(torch.float32) for k, v in new.items()}
@@ -386,16 +469,21 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
 
     def fit_em(self, n_rounds: int = 10, inner_iter: int = 10,
                update=("Phi", "Q", "R", "Sigma0"), phi_structure="full",
-               tolerance: float = 1e-4, verbose: bool = True):
+               tolerance: float = 1e-4, verbose: bool = True, smoothed=False):
         """Variational EM: ``n_rounds`` rounds of ``fit(max_iter=inner_iter)``
         followed by ``m_step(update, phi_structure)``.  ``history["em"]`` gains
         one m_step dictionary per round; ``history["elbo"]`` and
         ``history["reconstruction_error"]`` keep growing as repeated fit() calls
-        make them."""
+        make them.  smoothed=True: every M-step uses the statistics of the
+        smoothed posterior; F and the closed forms are the same (F is linear in
+        the statistics)."""
+        if smoothed and self._time_sharded():
+            raise NotImplementedError("smoothed=True is not available on a time-sharded run")
         em = self.history.setdefault("em", [])
         for k in range(int(n_rounds)):
             self.fit(max_iter=inner_iter, tolerance=tolerance, verbose=False)
-            res = self.m_step(update=update, phi_structure=phi_structure, apply=True)
+            res = self.m_step(update=update, phi_structure=phi_structure, apply=True,
+                              smoothed=smoothed)
             em.append(res)
             if verbose:
                 print(f"EM round {k:3d} | F: {res['objective_before']:.4f} -> "

@@ -31,10 +31,13 @@ UPDATES = ("Phi", "Q", "R", "Sigma0")
 PHI_STRUCTURES = ("full", "scalar")
 
 
-def combine(state: torch.Tensor, dyad: torch.Tensor) -> dict:
+def combine(state: torch.Tensor, dyad: torch.Tensor, cross=None) -> dict:
     """Per-slice rows in global time order (state (T, 2, d, d), dyad (T, 4),
     fp64, CPU) -> the statistics.  Slices are added one by one in time order,
-    so every caller that holds the same rows gets the same bits."""
+    so every caller that holds the same rows gets the same bits.  ``cross``
+    (T, d, d), optional: per-slice sums of the lag-one cross-covariances
+    Cov(x_t, x_t-1) of a q that is not factorised across time (ame_smooth's
+    lag_sum); slices 1.. are added into A10 after the mean part, in time order."""
     state = state.to("cpu", torch.float64)
     dyad = dyad.to("cpu", torch.float64)
     T, d = int(state.shape[0]), int(state.shape[2])
@@ -45,6 +48,10 @@ def combine(state: torch.Tensor, dyad: torch.Tensor) -> dict:
         A11 += state[t, 0]
         A00 += state[t - 1, 0]
         A10 += state[t, 1]
+    if cross is not None:
+        cross = cross.to("cpu", torch.float64)
+        for t in range(1, T):
+            A10 += cross[t]
     s = torch.zeros(4, dtype=torch.float64)
     for t in range(T):
         s += dyad[t]
