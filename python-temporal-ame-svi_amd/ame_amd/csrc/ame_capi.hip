@@ -229,9 +229,40 @@ static int device_cus() {
 
 static bool v2_block_in_lds(int n, int r) { return !sweep_lds_layout(n, r, 0).m_global; }
 static bool v2_single_fits(int n, int r) { return sweep_lds_layout(n, r, 1).total <= AME_LDS_MAX; }
-static bool is_concrete(int k) {
-    return k == AME_SWEEP_V3 || k == AME_SWEEP_V2_LDS || k == AME_SWEEP_V2_HBM || k == AME_SWEEP_V2_WORKERS ||
-           k == AME_SWEEP_V2_PIPE || k == AME_SWEEP_V2_W6;
+
+// The concrete sweep kinds: the mode of the v2 kernel (ame_sweep.hip; modes
+// >= 2 have ame_v2_nworkers(mode) GEMV-worker workgroups beside each slice's
+// own) or V3_KERNEL, whether the kernel orders its slices on the device, and
+// the message of a request that does not fit (n and r; worker kinds: n and
+// T_local).  Every query below reads the mapping from here.
+#define V3_KERNEL (-1)
+struct sweep_kind_row {
+    int kind, mode;
+    bool orders_slices;
+    const char* nofit;
+};
+static const sweep_kind_row g_kinds[] = {
+    {AME_SWEEP_V3, V3_KERNEL, true, "ame_sweep: the v3 sweep does not fit n=%d, r=%d"},
+    {AME_SWEEP_V2_LDS, 0, false, "ame_sweep: the (U,V) block of n=%d, r=%d does not fit in LDS"},
+    {AME_SWEEP_V2_HBM, 1, false, "ame_sweep: the v2 sweep does not fit n=%d, r=%d"},
+    {AME_SWEEP_V2_WORKERS, 2, false, "ame_sweep: GEMV workers do not fit n=%d, T_local=%d"},
+    {AME_SWEEP_V2_PIPE, 3, true,
+     "ame_sweep: the pipelined GEMV-worker sweep does not fit n=%d, T_local=%d"},
+    {AME_SWEEP_V2_W6, 4, false, "ame_sweep: the six-worker sweep does not fit n=%d, T_local=%d"},
+};
+
+static const sweep_kind_row* kind_row(int kind) {
+    for (const sweep_kind_row& k : g_kinds)
+        if (k.kind == kind) return &k;
+    return nullptr;
+}
+static bool is_concrete(int k) { return kind_row(k) != nullptr; }
+
+static bool kind_fits(const sweep_kind_row& k, const ame_dims* d) {
+    if (k.mode == V3_KERNEL) return ame_sweep3_supported(d->n, d->r);
+    if (k.mode == 0) return v2_block_in_lds(d->n, d->r);
+    if (k.mode == 1) return v2_single_fits(d->n, d->r);
+    return ame_sweep_workers_fit(d, k.mode);
 }
 
 // Request -> concrete kernel for these dims (-1 + message when it cannot run).
@@ -250,41 +281,21 @@ static int resolve_kind(const ame_dims* d, int request) {
             if (v2_block_in_lds(n, r)) return AME_SWEEP_V2_LDS;
             if (v2_single_fits(n, r)) return AME_SWEEP_V2_HBM;
             return fail("ame_sweep: no sweep kernel fits n=%d, r=%d", n, r);
-        case AME_SWEEP_V3:
-            if (ame_sweep3_supported(n, r)) return AME_SWEEP_V3;
-            return fail("ame_sweep: the v3 sweep does not fit n=%d, r=%d", n, r);
-        case AME_SWEEP_V2_LDS:
-            if (v2_block_in_lds(n, r)) return AME_SWEEP_V2_LDS;
-            return fail("ame_sweep: the (U,V) block of n=%d, r=%d does not fit in LDS", n, r);
-        case AME_SWEEP_V2_HBM:
-            if (v2_single_fits(n, r)) return AME_SWEEP_V2_HBM;
-            return fail("ame_sweep: the v2 sweep does not fit n=%d, r=%d", n, r);
-        case AME_SWEEP_V2_WORKERS:
-            if (ame_sweep_workers_fit(d, 2)) return AME_SWEEP_V2_WORKERS;
-            return fail("ame_sweep: GEMV workers do not fit n=%d, T_local=%d", n, d->T_local);
-        case AME_SWEEP_V2_PIPE:
-            if (ame_sweep_workers_fit(d, 3)) return AME_SWEEP_V2_PIPE;
-            return fail("ame_sweep: the pipelined GEMV-worker sweep does not fit n=%d, T_local=%d",
-                        n, d->T_local);
-        case AME_SWEEP_V2_W6:
-            if (ame_sweep_workers_fit(d, 4)) return AME_SWEEP_V2_W6;
-            return fail("ame_sweep: the six-worker sweep does not fit n=%d, T_local=%d", n, d->T_local);
-        default:
-            return fail("ame_sweep: unknown sweep kind request %d", request);
+        default: {
+            const sweep_kind_row* k = kind_row(request);
+            if (!k) return fail("ame_sweep: unknown sweep kind request %d", request);
+            if (kind_fits(*k, d)) return k->kind;
+            return fail(k->nofit, n, k->mode >= 2 ? d->T_local : r);
+        }
     }
 }
 
 long long ame_sweep_lds_bytes(int n, int r, int kind) {
     if (!r_supported(r) || n < 1) return 0;
-    switch (kind) {
-        case AME_SWEEP_V3: return ame_sweep3_supported(n, r) ? ame_sweep3_lds(n, r) : 0;
-        case AME_SWEEP_V2_LDS: return ame_v2_mode_lds(n, r, 0);
-        case AME_SWEEP_V2_HBM: return ame_v2_mode_lds(n, r, 1);
-        case AME_SWEEP_V2_WORKERS: return ame_v2_mode_lds(n, r, 2);
-        case AME_SWEEP_V2_PIPE: return ame_v2_mode_lds(n, r, 3);
-        case AME_SWEEP_V2_W6: return ame_v2_mode_lds(n, r, 4);
-        default: return 0;
-    }
+    const sweep_kind_row* k = kind_row(kind);
+    if (!k) return 0;
+    if (k->mode == V3_KERNEL) return ame_sweep3_supported(n, r) ? ame_sweep3_lds(n, r) : 0;
+    return ame_v2_mode_lds(n, r, k->mode);
 }
 
 int ame_sweep_max_slices(int n, int r, int request) {
@@ -298,49 +309,32 @@ int ame_sweep_max_slices(int n, int r, int request) {
         case AME_SWEEP_V2_SINGLE:
             if (v2_block_in_lds(n, r)) return ame_sweep_blocks_per_cu(n, r, 0) * cus;
             return v2_single_fits(n, r) ? ame_sweep_blocks_per_cu(n, r, 1) * cus : 0;
-        case AME_SWEEP_V3:
-            return ame_sweep3_supported(n, r) ? ame_sweep3_blocks_per_cu(n, r) * cus : 0;
-        case AME_SWEEP_V2_LDS:
-            return v2_block_in_lds(n, r) ? ame_sweep_blocks_per_cu(n, r, 0) * cus : 0;
-        case AME_SWEEP_V2_HBM:
-            return v2_single_fits(n, r) ? ame_sweep_blocks_per_cu(n, r, 1) * cus : 0;
-        case AME_SWEEP_V2_WORKERS:
-            return ame_sweep_blocks_per_cu(n, r, 2) * cus / (1 + AME_GW);
-        case AME_SWEEP_V2_PIPE: {
+        default: {
+            const sweep_kind_row* k = kind_row(request);
+            if (!k) return 0;
+            // kind 22 answers what the chip holds whether or not one slice's
+            // launch fits (resolve_kind decides that per launch); every other
+            // kind answers 0 when a one-slice launch does not fit
             ame_dims one = {n, r, 1, 0, 1, 0};
-            if (!ame_sweep_workers_fit(&one, 3)) return 0;
-            return ame_sweep_blocks_per_cu(n, r, 3) * cus / (1 + AME_GW_P);
+            if (k->kind != AME_SWEEP_V2_WORKERS && !kind_fits(*k, &one)) return 0;
+            if (k->mode == V3_KERNEL) return ame_sweep3_blocks_per_cu(n, r) * cus;
+            const int per_slice = k->mode >= 2 ? 1 + ame_v2_nworkers(k->mode) : 1;
+            return ame_sweep_blocks_per_cu(n, r, k->mode) * cus / per_slice;
         }
-        case AME_SWEEP_V2_W6: {
-            ame_dims one = {n, r, 1, 0, 1, 0};
-            if (!ame_sweep_workers_fit(&one, 4)) return 0;
-            return ame_sweep_blocks_per_cu(n, r, 4) * cus / (1 + AME_GW_6);
-        }
-        default:
-            return 0;
     }
 }
 
 int ame_sweep_slice_workgroups(int kind) {
-    switch (kind) {
-        case AME_SWEEP_V3:
-        case AME_SWEEP_V2_LDS:
-        case AME_SWEEP_V2_HBM: return 1;
-        case AME_SWEEP_V2_WORKERS: return 1 + ame_v2_nworkers(2);
-        case AME_SWEEP_V2_PIPE: return 1 + ame_v2_nworkers(3);
-        case AME_SWEEP_V2_W6: return 1 + ame_v2_nworkers(4);
-        default: return fail("ame_sweep_slice_workgroups: %d is not a concrete sweep kind", kind);
-    }
+    const sweep_kind_row* k = kind_row(kind);
+    if (!k) return fail("ame_sweep_slice_workgroups: %d is not a concrete sweep kind", kind);
+    return k->mode >= 2 ? 1 + ame_v2_nworkers(k->mode) : 1;
 }
 
 int ame_sweep_orders_slices(int n, int r, int kind) {
     if (!r_supported(r) || n < 2) return 0;
-    if (kind == AME_SWEEP_V3) return ame_sweep3_supported(n, r) ? 1 : 0;
-    if (kind == AME_SWEEP_V2_PIPE) {
-        ame_dims one = {n, r, 1, 0, 1, 0};
-        return ame_sweep_workers_fit(&one, 3) ? 1 : 0;
-    }
-    return 0;
+    const sweep_kind_row* k = kind_row(kind);
+    ame_dims one = {n, r, 1, 0, 1, 0};
+    return k && k->orders_slices && kind_fits(*k, &one) ? 1 : 0;
 }
 
 int ame_sweep_kind(const ame_dims* dims, int request) {
@@ -350,17 +344,14 @@ int ame_sweep_kind(const ame_dims* dims, int request) {
 
 long long ame_sweep_work_size(const ame_dims* dims, int kind) {
     if (check_dims(dims)) return -1;
-    switch (kind) {
-        case AME_SWEEP_V3: return ame_sweep3_work_doubles(dims);
-        case AME_SWEEP_V2_LDS: return 0;
-        // [T_local][n][2r] fp32 (U,V) copy
-        case AME_SWEEP_V2_HBM: return ((long long)dims->T_local * dims->n * 2 * dims->r + 1) / 2;
-        // partial ring, then the precomputed right AR terms
-        case AME_SWEEP_V2_WORKERS: return ame_v2_ring_doubles(dims, 2) + ame_v2_arr_doubles(dims);
-        case AME_SWEEP_V2_PIPE: return ame_v2_ring_doubles(dims, 3) + ame_v2_arr_doubles(dims);
-        case AME_SWEEP_V2_W6: return ame_v2_ring_doubles(dims, 4) + ame_v2_arr_doubles(dims);
-        default: return fail("ame_sweep_work_size: %d is not a concrete sweep kind", kind);
-    }
+    const sweep_kind_row* k = kind_row(kind);
+    if (!k) return fail("ame_sweep_work_size: %d is not a concrete sweep kind", kind);
+    if (k->mode == V3_KERNEL) return ame_sweep3_work_doubles(dims);
+    if (k->mode == 0) return 0;
+    // [T_local][n][2r] fp32 (U,V) copy
+    if (k->mode == 1) return ((long long)dims->T_local * dims->n * 2 * dims->r + 1) / 2;
+    // partial ring, then the precomputed right AR terms
+    return ame_v2_ring_doubles(dims, k->mode) + ame_v2_arr_doubles(dims);
 }
 
 long long ame_pack_y_size(const ame_dims* dims) {
@@ -393,7 +384,7 @@ int ame_sweep(const ame_dims* dims, const ame_sweep_args* a, void* stream) {
         return fail("ame_sweep: the work buffer holds %d doubles, kind %d needs more", (int)a->work_doubles, kind);
     if (a->wait_epoch != 0 && (!ame_sweep_orders_slices(dims->n, dims->r, kind) || !a->done))
         return fail("ame_sweep: wait_epoch needs a kernel that orders slices (kind %d) and a done array", kind);
-    const int maxs = (kind == AME_SWEEP_V2_WORKERS || kind == AME_SWEEP_V2_PIPE || kind == AME_SWEEP_V2_W6)
+    const int maxs = kind_row(kind)->mode >= 2
                           ? dims->T_local   // resolve_kind checked that the launch co-resides
                           : ame_sweep_max_slices(dims->n, dims->r, kind);
     if (dims->T_local > maxs)

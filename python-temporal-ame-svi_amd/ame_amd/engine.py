@@ -45,6 +45,8 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .plan import (ELBO_READ_STEPS, FILL_STEPS_PER_SLICE, MAX_SPEC_DEPTH,  # noqa: F401 (re-exported)
+                   LibCaps, derive_spec_depth, plan_sweeps, slice_groups)
 
 LOG2PI = math.log(2.0 * math.pi)
 VARIANTS = {"good": _lib.AME_GOOD, "bad": _lib.AME_BAD, "naive": _lib.AME_NAIVE}
@@ -114,28 +116,6 @@ class EngineOptions:
         if bad:
             raise ValueError(f"unknown engine option(s) {sorted(bad)}; known: {sorted(names)}")
         return cls(**opts)
-
-
-# Queue-depth model.  In the pipelined steady state with period
-# P (about one slice's chain of n node steps) the host reads iteration k's ELBO
-# once sweep k has finished on the LAST slice of the LAST rank, i.e. after the
-# wavefront's fill over all T_total slices plus one chain plus the ELBO kernels
-# and the all_reduce; by then sweep k + 1 + depth must already be queued:
-#     (1 + depth) P >= fill + C + delta,   fill = F (T_total - 1) steps.
-# F = node steps of lag per slice: 2.94 measured in round 4 (lane start offset
-# 890 us over 127 slices at 2.38 us per step, profiles/r04_v3_stamps_head.txt;
-# 2.6 in round 1), rounded up to 3.0 -- a deeper queue only costs a state slot;
-# delta ~ 128 steps (0.33 ms).
-FILL_STEPS_PER_SLICE = 3.0
-ELBO_READ_STEPS = 128
-MAX_SPEC_DEPTH = 8
-
-
-def derive_spec_depth(n: int, T_total: int) -> int:
-    """Smallest queue depth the model above needs, at least 2 (measured best on
-    one GPU), at most MAX_SPEC_DEPTH."""
-    need = math.ceil((FILL_STEPS_PER_SLICE * (T_total - 1) + ELBO_READ_STEPS) / max(1, n))
-    return max(2, min(MAX_SPEC_DEPTH, need))
 
 
 # Sweep epochs are unique within the process: every engine starts above the
@@ -253,29 +233,54 @@ def assemble(out, n, T, d, variant, C: Constants):
             "elbo": loglik + prior0 + trans + ent, "recon": recon}
 
 
-def slice_groups(T_local: int, max_slices: int, force: int = 0):
-    """Consecutive groups [(offset, size)] of the local slices that each fit on
-    the chip at once (a sweep's slices spin on each other, so all slices of one
-    launch must be co-resident).  The groups of one sweep run one after another
-    on one stream; group g+1's first slice takes slice (g's last)'s new means
-    from the hand-off granules group g left behind, so the Gauss-Seidel order
-    is the same as one launch over all slices (reference: the t loop of
-    structured_mf.py:240 has no limit on T)."""
-    cap = max_slices if force <= 0 else min(force, max_slices)
-    if cap < 1:
-        raise RuntimeError("ame_amd: no sweep workgroup fits on this device")
-    k = -(-T_local // cap)
-    base, extra = divmod(T_local, k)
-    out, off = [], 0
-    for g in range(k):
-        sz = base + (1 if g < extra else 0)
-        out.append((off, sz))
-        off += sz
-    return out
+class _ElboCall:
+    """The with-block of DeviceEngine._elbo_call: the CU-masked ELBO stream is
+    ordered after everything queued on the main one, and later main-stream
+    work (reading out) after it.  A class, not a generator: this runs twice per
+    fit() iteration on the host's critical path.  A launch that raises leaves
+    the block without the closing event, as the caller's exception is the news."""
+    __slots__ = ("eng", "name", "st", "tok")
+
+    def __init__(self, eng, name):
+        self.eng, self.name = eng, name
+
+    def __enter__(self):
+        eng = self.eng
+        st = self.st = eng._elbo_stream()
+        if st is not eng.stream:
+            ev = torch.cuda.Event()
+            ev.record(eng.stream)
+            st.wait_event(ev)
+        self.tok = eng._tic(self.name, st) if eng.timing else None
+        return ctypes.c_void_p(st.cuda_stream)
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            eng = self.eng
+            if self.tok is not None:
+                eng._toc(self.tok)
+            if self.st is not eng.stream:
+                ev = torch.cuda.Event()
+                ev.record(self.st)
+                eng.stream.wait_event(ev)
+        return False
+
+
+def _plan_field(name):
+    return property(lambda self: getattr(self.plan, name), doc=f"SweepPlan.{name} of this engine")
 
 
 class DeviceEngine:
     """HBM-resident state of one VI run on one GPU (one time shard)."""
+
+    max_slices = _plan_field("max_slices")
+    groups = _plan_field("groups")
+    group_kinds = _plan_field("group_kinds")
+    sweep_kind = _plan_field("sweep_kind")
+    resident_slots = _plan_field("resident_slots")
+    pipelined = _plan_field("pipelined")
+    coresident_launches = _plan_field("coresident_launches")
+    spec_depth = _plan_field("spec_depth")
 
     def __init__(self, model, variant: str, lr: float, X_mean: torch.Tensor,
                  X_cov: torch.Tensor, device=None, shard: Optional[Shard] = None,
@@ -324,85 +329,20 @@ class DeviceEngine:
         self.epoch = _epoch_base()
         if self.halo is not None:   # every rank's sweep k carries the same epoch
             self.epoch = self.halo.agree_max(self, self.epoch)
-        self.max_slices = int(self.L.ame_sweep_max_slices(self.n, self.r, opt.sweep_kernel))
-        if self.max_slices < 1:
-            raise RuntimeError(f"ame_amd: no sweep kernel fits n={self.n}, r={self.r} "
-                               f"(request {opt.sweep_kernel})")
-        self._cu_split = None
-        if opt.elbo_cus:
-            # ELBO beside the sweep: the sweep's launch must fit the CUs left to it
-            # (workgroups per slice from the library, one CU each)
-            per_slice = None
-            if opt.sweep_kernel in (_lib.AME_SWEEP_V2_WORKERS, _lib.AME_SWEEP_V2_W6):
-                per_slice = int(self.L.ame_sweep_slice_workgroups(opt.sweep_kernel))
-            cus = int(torch.cuda.get_device_properties(self.dev).multi_processor_count)
-            if per_slice is None or per_slice < 1 or not 0 < int(opt.elbo_cus) < cus:
-                raise ValueError("elbo_cus needs sweep_kernel 22 or 24 and 0 < elbo_cus < "
-                                 f"{cus} CUs (got {opt.elbo_cus}, kernel {opt.sweep_kernel})")
-            self.max_slices = min(self.max_slices, (cus - int(opt.elbo_cus)) // per_slice)
-            if self.max_slices < 1:
-                raise ValueError(f"elbo_cus={opt.elbo_cus} leaves no room for a slice")
-            self._cu_split = (int(opt.elbo_cus), cus)
-        req = opt.sweep_kernel
-        if req in (_lib.AME_SWEEP_AUTO, _lib.AME_SWEEP_V2_AUTO) and (
-                req == _lib.AME_SWEEP_V2_AUTO
-                or int(self.L.ame_sweep_max_slices(self.n, self.r, _lib.AME_SWEEP_V3)) < 1):
-            # beyond v3's reach the GEMV-worker sweep (kind 22) in slice groups of
-            # what co-resides beats ONE launch of the single-workgroup sweep over
-            # all slices: config 5 at T = 256 on one GPU, 8 groups of 32 vs kind 21,
-            # 285-302 vs 580 ms per iteration; the pipelined kind 23 in overlapping
-            # groups measured the same, 274-291 ms, and loses at
-            # T_local = 32, so kind 22 stays the choice.  AUTO picks kind 22
-            # whenever T_local fits one launch
-            w = int(self.L.ame_sweep_max_slices(self.n, self.r, _lib.AME_SWEEP_V2_WORKERS))
-            if 1 <= w < min(sh.T_local, self.max_slices):
-                gd = _lib.ame_dims(self.n, self.r, w, sh.t_begin, sh.T_total, self.vcode)
-                if int(self.L.ame_sweep_kind(ctypes.byref(gd), req)) == _lib.AME_SWEEP_V2_WORKERS:
-                    self.max_slices = w
-        # Ranks of one time-sharded run that share this GPU share its CUs, and a
-        # spinning launch of one rank can wait on a slice of another (halo, back
-        # channel): all of them must be co-resident at once, so each rank
-        # budgets for 1/k of the chip (co-residency rule)
+        # the sweep launches (ame_amd/plan.py); ranks that share this GPU share
+        # its CUs, and every rank must take the same path
+        caps = LibCaps(self.n, self.r, sh.t_begin, sh.T_total, self.vcode, dev)
         self.device_sharers = self.halo.device_sharers(self) if self.halo is not None else 1
-        if self.device_sharers > 1:
-            self.max_slices //= self.device_sharers
-            if self.max_slices < 1:
-                raise RuntimeError(f"ame_amd: {self.device_sharers} ranks share this GPU and one "
-                                   f"sweep slice (n={self.n}, r={self.r}) does not fit 1/"
-                                   f"{self.device_sharers} of it")
-        # Pipelined layout: a kernel that orders itself slice by slice on the
-        # device (done flags) runs with TWO launches co-resident -- consecutive
-        # sweeps, and consecutive slice groups of one sweep -- so each launch gets
-        # at most half of what co-resides; the launches alternate over two
-        # streams
-        pipe_cap = 0
-        if opt.pipeline and self.max_slices >= 2:
-            half = self.max_slices // 2
-            pd = _lib.ame_dims(self.n, self.r, max(1, min(sh.T_local, half)), sh.t_begin,
-                               sh.T_total, self.vcode)
-            pk = int(self.L.ame_sweep_kind(ctypes.byref(pd), req))
-            if pk >= 0 and bool(self.L.ame_sweep_orders_slices(self.n, self.r, pk)):
-                pipe_cap = half
-        self.groups = slice_groups(sh.T_local, pipe_cap or self.max_slices, opt.slice_group)
-        # the kernel of each group size is resolved ONCE here and passed with
-        # every launch (ame_sweep rejects a launch whose buffers were sized for
-        # another kind); groups that run one after another share the scratch,
-        # pipelined launches alternate between two halves of it
-        self.group_kinds = {}
-        sws = 1
-        for size in sorted({sz for _, sz in self.groups}):
-            gd = _lib.ame_dims(self.n, self.r, size, sh.t_begin, sh.T_total, self.vcode)
-            k = int(self.L.ame_sweep_kind(ctypes.byref(gd), req))
-            if k < 0:
-                _lib.check(-1, "ame_sweep_kind")
-            w = int(self.L.ame_sweep_work_size(ctypes.byref(gd), k))
-            if w < 0:
-                _lib.check(-1, "ame_sweep_work_size")
-            self.group_kinds[size] = k
-            sws = max(sws, w)
-        self.sweep_kind = self.group_kinds[self.groups[0][1]]
+        self.plan = plan_sweeps(caps, self.n, sh.T_local, sh.T_total, opt, self.device_sharers)
+        if self.halo is not None and not self.halo.agree(self, self.plan.pipelined):
+            self.plan = self.plan.serial()
+        # ELBO before the speculative sweep (EngineOptions.elbo_first)
+        self.elbo_first = bool(opt.elbo_first)
+        if self.halo is not None:   # the collectives of sums() keep one order on every rank
+            self.elbo_first = self.halo.agree(self, self.elbo_first)
         self._out_host = None
         self._out_valid = False
+        self._cov_terms_valid = False
         self.timing = False       # record HIP events around each kernel launch
         self.events = []          # (name, start, end) while timing
         self.speculation = bool(opt.speculate)
@@ -410,57 +350,28 @@ class DeviceEngine:
         # consecutive sweeps (or, pipelined, consecutive launches) alternate
         # between two high-priority streams
         self.elbo_stream = None
-        if self._cu_split is None:
-            self.sweep_streams = [torch.cuda.Stream(device=self.dev, priority=-1) for _ in range(2)]
+        if self.plan.cu_split is None:
+            self.sweep_streams = [torch.cuda.Stream(device=dev, priority=-1) for _ in range(2)]
         else:
-            ec, cus = self._cu_split
+            ec, cus = self.plan.cu_split
             self.elbo_stream = self._cu_stream(0, ec)
             self.sweep_streams = [self._cu_stream(ec, cus - ec, slot) for slot in range(2)]
         self._launch_ctr = 0
-        self.done = torch.zeros(max(sh.T_local, 1), dtype=torch.int32, device=self.dev)
-        kinds = set(self.group_kinds.values())
-        # slice workgroups of this kind the whole chip holds at once
-        self.resident_slots = int(self.L.ame_sweep_max_slices(self.n, self.r, self.sweep_kind))
-        self.pipelined = (len(kinds) == 1 and pipe_cap > 0
-                          and bool(self.L.ame_sweep_orders_slices(self.n, self.r, self.sweep_kind))
-                          and 2 * max(sz for _, sz in self.groups) * self.device_sharers
-                          <= self.resident_slots
-                          and bool(opt.pipeline))
-        if self.halo is not None:   # every rank must take the same path
-            self.pipelined = self.halo.agree(self, self.pipelined)
-        # launches of this process that may spin at once (pipelined: one per
-        # sweep stream); the co-residency rule is
-        #     device_sharers * coresident_launches * largest group <= resident_slots
-        self.coresident_launches = 2 if self.pipelined else 1
-        # How many sweeps may run ahead of the committed state.  Pipelined sweeps
-        # overlap slice by slice, so a deeper queue keeps the wavefront full when
-        # its fill over all T slices (all ranks) exceeds one iteration: the host
-        # reads iteration k's ELBO only after sweep k has finished everywhere, and
-        # sweep k+depth must already be queued by then.
-        if opt.spec_depth is None:
-            self.spec_depth = derive_spec_depth(self.n, sh.T_total) if self.pipelined else 1
-        else:
-            self.spec_depth = int(opt.spec_depth)
-        if self.spec_depth < 1:
-            raise ValueError("spec_depth must be >= 1")
-        if not self.pipelined:
-            # A sweep that does not order itself slice by slice on the device must
-            # not start before the sweep that writes its input slot has finished;
-            # with more than one queued that is a serial chain anyway, so the
-            # queue is one deep (_launch_sweep also orders after the last one).
-            self.spec_depth = 1
-        # ELBO before the speculative sweep (EngineOptions.elbo_first)
-        self.elbo_first = bool(opt.elbo_first)
-        if self.halo is not None:   # the collectives of sums() keep one order on every rank
-            self.elbo_first = self.halo.agree(self, self.elbo_first)
-        # scratch per launch; pipelined, two launches run at once: two halves
-        self._work_half = sws
         with torch.cuda.device(dev):
-            self.sweep_work = torch.empty(sws * (2 if self.pipelined else 1), dtype=torch.float64,
-                                          device=dev)
+            self.done = torch.zeros(max(sh.T_local, 1), dtype=torch.int32, device=dev)
+            # scratch per launch; pipelined, two launches run at once: two halves
+            self.sweep_work = torch.empty(self.plan.work_doubles * self.coresident_launches,
+                                          dtype=torch.float64, device=dev)
             while len(self.xs) < self.spec_depth + 1:
                 self.xs.append(torch.empty_like(self.xs[0]))
                 self.covs.append(torch.empty_like(self.covs[0]))
+        # Scratch of the calls that run beside the sweep (predict, mstep_stats,
+        # smooth), grown to the largest need so far.  One buffer serves all
+        # three: they run one after another on the ELBO stream, none reads what
+        # it has not written in the same call (the buffer starts uninitialised),
+        # and none keeps a result there -- outputs are separate tensors, also
+        # those of smooth() that are fed back into mstep_stats / predict.
+        self._side_work = None
         self._host_ready = None
         # test hook only (tests/test_gpu_stale_epoch.py): False lets a pipelined
         # launch skip the wait for host-issued writes, to show the device's
@@ -487,21 +398,33 @@ class DeviceEngine:
             st = _CU_STREAMS[key] = torch.cuda.ExternalStream(p.value, device=self.dev)
         return st
 
-    def _elbo_stream_begin(self):
+    def _elbo_stream(self):
         """The stream the ELBO kernels run on: the main stream, or (elbo_cus) the
-        CU-masked ELBO stream ordered after everything queued on the main one."""
-        if self.elbo_stream is None:
-            return self.stream
-        ev = torch.cuda.Event()
-        ev.record(self.stream)
-        self.elbo_stream.wait_event(ev)
-        return self.elbo_stream
+        CU-masked ELBO stream."""
+        return self.stream if self.elbo_stream is None else self.elbo_stream
 
-    def _elbo_stream_end(self, st):
-        if st is not self.stream:   # later main-stream work (reading out) waits for it
-            ev = torch.cuda.Event()
-            ev.record(st)
-            self.stream.wait_event(ev)
+    def _elbo_call(self, name):
+        """``with self._elbo_call(name) as sp:`` launches on the ELBO stream (handle
+        sp), timed as `name` (kernel_ms)."""
+        return _ElboCall(self, name)
+
+    def _scratch(self, need):
+        """The shared scratch of the calls beside the sweep, at least `need` doubles."""
+        if self._side_work is None or self._side_work.numel() < need:
+            with torch.cuda.device(self.dev):
+                self._side_work = torch.empty(need, dtype=torch.float64, device=self.dev)
+        return self._side_work
+
+    def _slice_chunk(self, work_size, S):
+        """(slices per call, scratch) for S independent slices scored in whole
+        slices within PREDICT_WORK_DOUBLES; work_size is the library's query."""
+        one = _lib.ame_dims(self.n, self.r, 1, 0, 1, self.vcode)
+        per = int(work_size(ctypes.byref(one)))
+        if per < 0:
+            _lib.check(-1, work_size.__name__)
+        chunk = max(1, min(S, self.PREDICT_WORK_DOUBLES // per))
+        dims = _lib.ame_dims(self.n, self.r, chunk, 0, chunk, self.vcode)
+        return chunk, self._scratch(int(work_size(ctypes.byref(dims))))
 
     def _mark_host_writes(self):
         """Record the main-stream position after host-issued writes to the state
@@ -581,11 +504,12 @@ class DeviceEngine:
         over the two sweep streams, so launch j + 1 runs beside launch j and
         launch j + 2 queues behind launch j (at most two co-resident); otherwise
         a sweep's groups run in order on one stream."""
+        plan = self.plan
         src = self._specs[-1][1] if self._specs else self._cur
         dst = (src + 1) % len(self.xs)
         self.epoch += 1
         _note_epoch(self.epoch)
-        pipe = spec and self.pipelined and self.speculation
+        pipe = spec and plan.pipelined and self.speculation
         halo_in = halo_out = next_old = back_in = back_out = None
         if self.halo is not None:
             # a pipelined launch takes next_old from the back channel instead of a
@@ -618,15 +542,15 @@ class DeviceEngine:
 
         tok = None
         n, d, sh = self.n, self.d, self.shard
-        last = len(self.groups) - 1
+        last = len(plan.groups) - 1
         stream = None
-        for g, (off, size) in enumerate(self.groups):
-            if self.pipelined:
+        for g, (off, size) in enumerate(plan.groups):
+            if plan.pipelined:
                 par = self._launch_ctr & 1
                 self._launch_ctr += 1
             else:
                 par = 0
-            stream = self.sweep_streams[par if self.pipelined else (self.epoch & 1)]
+            stream = self.sweep_streams[par if plan.pipelined else (self.epoch & 1)]
             order(stream)
             if tok is None:
                 tok = self._tic("sweep", stream)
@@ -639,14 +563,14 @@ class DeviceEngine:
             g_next_old = next_old if g == last else at(self.xs[src], off + size, nd, 4)
             dims = _lib.ame_dims(n, self.r, size, sh.t_begin + off, sh.T_total, self.vcode)
             a = _lib.ame_sweep_args(
-                kind=self.group_kinds[size], work_doubles=self._work_half,
+                kind=plan.group_kinds[size], work_doubles=plan.work_doubles,
                 Yt=at(self.Yt, off, nn2, 4), x_old=at(self.xs[src], off, nd, 4),
                 x_new=at(self.xs[dst], off, nd, 4), next_old=g_next_old,
                 hand=at(self.hand, off, nd, 8), halo_in=g_halo_in, halo_out=g_halo_out,
                 cov=at(self.covs[src], off, ndd, 4), consts=_ptr(self.consts),
                 rinv=self.C.rinv4(), lr=self.lr, one_minus_lr=float(1.0 - self.lr),
                 epoch=self.epoch, status=_ptr(self.status),
-                work=at(self.sweep_work, par, self._work_half, 8),
+                work=at(self.sweep_work, par, plan.work_doubles, 8),
                 cov_new=at(self.covs[dst], off, ndd, 4), done=at(self.done, off, 1, 4),
                 wait_epoch=wait, back_out=back_out if g == 0 else None,
                 back_in=back_in if g == last else None,
@@ -693,7 +617,7 @@ class DeviceEngine:
         the host has already read."""
         if not self.speculation:
             return
-        want = min(int(ahead), self.spec_depth)
+        want = min(int(ahead), self.plan.spec_depth)
         while len(self._specs) < want:
             self._specs.append(self._launch_sweep(spec=True))
 
@@ -709,19 +633,15 @@ class DeviceEngine:
         """Covariance ELBO terms of the current covariances (no update)."""
         c = _lib.ame_cov_args(cov=_ptr(self.cov), consts=_ptr(self.consts),
                               cov_terms=_ptr(self.cov_terms))
-        st = self._elbo_stream_begin()
-        tok = self._tic("cov", st)
-        _lib.check(self.L.ame_cov(ctypes.byref(self.dims), ctypes.byref(c),
-                                  ctypes.c_void_p(st.cuda_stream)), "ame_cov")
-        self._toc(tok)
-        self._elbo_stream_end(st)
+        with self._elbo_call("cov") as sp:
+            _lib.check(self.L.ame_cov(ctypes.byref(self.dims), ctypes.byref(c), sp), "ame_cov")
         self._cov_terms_valid = True
 
     def launch_elbo(self, pairs_only=False):
         """The ELBO / MSE sums of the current state into self.out.  pairs_only
         (diagnostic timing): the pair kernel alone through ame_elbo_pairs_diag,
         which writes no sums."""
-        if not pairs_only and not getattr(self, "_cov_terms_valid", False):
+        if not pairs_only and not self._cov_terms_valid:
             self.refresh_cov_terms()
         prev_final = None
         if self.halo is not None and not pairs_only:
@@ -731,19 +651,10 @@ class DeviceEngine:
             cov_terms=_ptr(self.cov_terms), consts=_ptr(self.consts), phi=_ptr(self.phi),
             rinv=self.C.rinv4(), swap_consistent=1 if self.swap_consistent else 0,
             work=_ptr(self.work), out=_ptr(self.out), pairs_kernel=self.options.pairs_kernel)
-        st = self._elbo_stream_begin()
-        sp = ctypes.c_void_p(st.cuda_stream)
-        if pairs_only:
-            tok = self._tic("pairs", st)
-            _lib.check(self.L.ame_elbo_pairs_diag(ctypes.byref(self.dims), ctypes.byref(e), sp),
-                       "ame_elbo_pairs_diag")
-            self._toc(tok)
-            self._elbo_stream_end(st)
-            return
-        tok = self._tic("elbo", st)
-        _lib.check(self.L.ame_elbo(ctypes.byref(self.dims), ctypes.byref(e), sp), "ame_elbo")
-        self._toc(tok)
-        self._elbo_stream_end(st)
+        launch, what = ((self.L.ame_elbo_pairs_diag, "ame_elbo_pairs_diag") if pairs_only
+                        else (self.L.ame_elbo, "ame_elbo"))
+        with self._elbo_call("pairs" if pairs_only else "elbo") as sp:
+            _lib.check(launch(ctypes.byref(self.dims), ctypes.byref(e), sp), what)
 
     def sums(self, speculate=0):
         """The 8 fp64 sums for the current state (all ranks reduced).  With
@@ -848,42 +759,30 @@ class DeviceEngine:
         assert tuple(x.shape) == (S, n, d) and tuple(cov.shape) == (S, n, d, d)
         assert x.is_contiguous() and cov.is_contiguous()
         nl = len(zsq)
-        one = _lib.ame_dims(n, self.r, 1, 0, 1, self.vcode)
-        per = int(self.L.ame_predict_work_size(ctypes.byref(one)))
-        if per < 0:
-            _lib.check(-1, "ame_predict_work_size")
-        chunk = max(1, min(S, self.PREDICT_WORK_DOUBLES // per))
-        dims = _lib.ame_dims(n, self.r, chunk, 0, chunk, self.vcode)
-        need = int(self.L.ame_predict_work_size(ctypes.byref(dims)))
+        chunk, wk = self._slice_chunk(self.L.ame_predict_work_size, S)
         with torch.cuda.device(self.dev):
-            wk = getattr(self, "_predict_work", None)
-            if wk is None or wk.numel() < need:
-                wk = self._predict_work = torch.empty(need, dtype=torch.float64, device=self.dev)
             sums = torch.zeros(S, _lib.AME_PREDICT_SUMS, dtype=torch.float64,
                                device=self.dev) if Yt is not None else None
             dense = None
             if block is not None:
                 i0, i1, j0, j1 = (int(v) for v in block)
                 dense = torch.empty(S, i1 - i0, j1 - j0, 5, dtype=torch.float32, device=self.dev)
-        st = self._elbo_stream_begin()
-        sp = ctypes.c_void_p(st.cuda_stream)
-        tok = self._tic("predict", st)
-        for s0 in range(0, S, chunk):
-            s1 = min(S, s0 + chunk)
-            dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
-            a = _lib.ame_predict_args(
-                x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]), Yt=_ptr(Yt[s0:s1]) if Yt is not None else None,
-                noise=self.noise4(include_noise), n_levels=nl,
-                zsq=(ctypes.c_double * _lib.AME_PREDICT_MAX_LEVELS)(*zsq),
-                csq=(ctypes.c_double * _lib.AME_PREDICT_MAX_LEVELS)(*csq),
-                sums=_ptr(sums[s0:s1]) if sums is not None else None,
-                dense=_ptr(dense[s0:s1]) if dense is not None else None,
-                work=_ptr(wk))
-            if block is not None:
-                a.i0, a.i1, a.j0, a.j1 = i0, i1, j0, j1
-            _lib.check(self.L.ame_predict(ctypes.byref(dm), ctypes.byref(a), sp), "ame_predict")
-        self._toc(tok)
-        self._elbo_stream_end(st)
+        with self._elbo_call("predict") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_predict_args(
+                    x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]),
+                    Yt=_ptr(Yt[s0:s1]) if Yt is not None else None,
+                    noise=self.noise4(include_noise), n_levels=nl,
+                    zsq=(ctypes.c_double * _lib.AME_PREDICT_MAX_LEVELS)(*zsq),
+                    csq=(ctypes.c_double * _lib.AME_PREDICT_MAX_LEVELS)(*csq),
+                    sums=_ptr(sums[s0:s1]) if sums is not None else None,
+                    dense=_ptr(dense[s0:s1]) if dense is not None else None,
+                    work=_ptr(wk))
+                if block is not None:
+                    a.i0, a.i1, a.j0, a.j1 = i0, i1, j0, j1
+                _lib.check(self.L.ame_predict(ctypes.byref(dm), ctypes.byref(a), sp), "ame_predict")
         return sums, dense
 
     # ------------------------------------------------------------------
@@ -900,36 +799,23 @@ class DeviceEngine:
         n, d, sh = self.n, self.d, self.shard
         TL = sh.T_local
         prev_final = self.halo.prev_final(self) if self.halo is not None else None
-        one = _lib.ame_dims(n, self.r, 1, 0, 1, self.vcode)
-        per = int(self.L.ame_mstep_work_size(ctypes.byref(one)))
-        if per < 0:
-            _lib.check(-1, "ame_mstep_work_size")
-        chunk = max(1, min(TL, self.PREDICT_WORK_DOUBLES // per))
-        dims = _lib.ame_dims(n, self.r, chunk, 0, chunk, self.vcode)
-        need = int(self.L.ame_mstep_work_size(ctypes.byref(dims)))
+        chunk, wk = self._slice_chunk(self.L.ame_mstep_work_size, TL)
         if x is None:
             x, cov = self.x_a, self.cov
         with torch.cuda.device(self.dev):
-            wk = getattr(self, "_mstep_work", None)
-            if wk is None or wk.numel() < need:
-                wk = self._mstep_work = torch.empty(need, dtype=torch.float64, device=self.dev)
             state = torch.empty(TL, 2, d, d, dtype=torch.float64, device=self.dev)
             dyad = torch.empty(TL, 4, dtype=torch.float64, device=self.dev)
-        st = self._elbo_stream_begin()
-        sp = ctypes.c_void_p(st.cuda_stream)
-        tok = self._tic("mstep", st)
-        for s0 in range(0, TL, chunk):
-            s1 = min(TL, s0 + chunk)
-            dm = _lib.ame_dims(n, self.r, s1 - s0, sh.t_begin + s0, sh.T_total, self.vcode)
-            a = _lib.ame_mstep_args(
-                x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]),
-                prev_final=prev_final if s0 == 0 else _ptr(x[s0 - 1]),
-                Yt=_ptr(self.Yt[s0:s1]), state=_ptr(state[s0:s1]), dyad=_ptr(dyad[s0:s1]),
-                work=_ptr(wk))
-            _lib.check(self.L.ame_mstep_stats(ctypes.byref(dm), ctypes.byref(a), sp),
-                       "ame_mstep_stats")
-        self._toc(tok)
-        self._elbo_stream_end(st)
+        with self._elbo_call("mstep") as sp:
+            for s0 in range(0, TL, chunk):
+                s1 = min(TL, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, sh.t_begin + s0, sh.T_total, self.vcode)
+                a = _lib.ame_mstep_args(
+                    x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]),
+                    prev_final=prev_final if s0 == 0 else _ptr(x[s0 - 1]),
+                    Yt=_ptr(self.Yt[s0:s1]), state=_ptr(state[s0:s1]), dyad=_ptr(dyad[s0:s1]),
+                    work=_ptr(wk))
+                _lib.check(self.L.ame_mstep_stats(ctypes.byref(dm), ctypes.byref(a), sp),
+                           "ame_mstep_stats")
         return state, dyad
 
     # ------------------------------------------------------------------
@@ -961,29 +847,24 @@ class DeviceEngine:
         self.discard_speculation()
         n, d, T = self.n, self.d, self.shard.T_local
         chunk = self.smooth_chunk()
-        need = int(self.L.ame_smooth_work_size(ctypes.byref(self.dims), chunk))
+        wk = self._scratch(int(self.L.ame_smooth_work_size(ctypes.byref(self.dims), chunk)))
         x = self.x_a
         with torch.cuda.device(self.dev):
-            wk = getattr(self, "_smooth_work", None)
-            if wk is None or wk.numel() < need:
-                wk = self._smooth_work = torch.empty(need, dtype=torch.float64, device=self.dev)
-            mean = torch.empty(T, n, d, dtype=torch.float32, device=self.dev)
+            mean =torch.empty(T, n, d, dtype=torch.float32, device=self.dev)
             cov = torch.empty(T, n, d, d, dtype=torch.float32, device=self.dev)
             cross = torch.empty(T, n, d, d, dtype=torch.float32, device=self.dev)
             lag = torch.empty(T, d, d, dtype=torch.float64, device=self.dev)
             fail = torch.zeros(_lib.AME_SMOOTH_FAIL_WORDS, dtype=torch.int32, device=self.dev)
-        st = self._elbo_stream_begin()
-        sp = ctypes.c_void_p(st.cuda_stream)
-        tok = self._tic("smooth", st)
-        for i0 in range(0, n, chunk):
-            a = _lib.ame_smooth_args(
-                x=_ptr(x), Yt=_ptr(self.Yt), consts=_ptr(self.consts), rinv=self.C.rinv4(),
-                i0=i0, i1=min(n, i0 + chunk), stages=int(stages), mean=_ptr(mean), cov=_ptr(cov),
-                cross=_ptr(cross), lag_sum=_ptr(lag), fail=_ptr(fail), work=_ptr(wk),
-                work_doubles=wk.numel())
-            _lib.check(self.L.ame_smooth(ctypes.byref(self.dims), ctypes.byref(a), sp), "ame_smooth")
-        self._toc(tok)
-        self._elbo_stream_end(st)
+        with self._elbo_call("smooth") as sp:
+            for i0 in range(0, n, chunk):
+                a = _lib.ame_smooth_args(
+                    x=_ptr(x), Yt=_ptr(self.Yt), consts=_ptr(self.consts), rinv=self.C.rinv4(),
+                    i0=i0, i1=min(n, i0 + chunk), stages=int(stages), mean=_ptr(mean), cov=_ptr(cov),
+                    cross=_ptr(cross), lag_sum=_ptr(lag), fail=_ptr(fail), work=_ptr(wk),
+                    work_doubles=wk.numel())
+                _lib.check(self.L.ame_smooth(ctypes.byref(self.dims), ctypes.byref(a), sp),
+                           "ame_smooth")
+        st = self._elbo_stream()
         for t in (x, self.Yt, self.consts, wk, mean, cov, cross, lag, fail):
             t.record_stream(st)
         if check:

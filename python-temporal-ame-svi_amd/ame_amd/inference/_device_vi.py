@@ -74,6 +74,8 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         self._distributed = distributed
         self._engine_options = EngineOptions.coerce(engine_options)
         self._engine: Optional[DeviceEngine] = None
+        self._halo = None       # the engine's TimeShardHalo (time-sharded runs)
+        self._spec_next = 0     # iterations fit() still has to go (speculation window)
         self._host = {"mean": None, "cov": None}
         self._ver = {"mean": None, "cov": None}
         self._stale = {"mean": False, "cov": False}
@@ -130,7 +132,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         """Whether this run is (or, before the engine exists, will be) time-sharded;
         decided without a collective."""
         if self._engine is not None:
-            return getattr(self, "_halo", None) is not None
+            return self._halo is not None
         return self._wants_halo()
 
     def _wants_halo(self) -> bool:
@@ -172,7 +174,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         return self._engine
 
     def _gather(self, local, axis):
-        halo = getattr(self, "_halo", None)
+        halo = self._halo
         if halo is None:
             return local.detach().to("cpu").contiguous()
         return halo.gather_time(local, axis)
@@ -194,7 +196,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         self._spec_next = 0
         if self._engine is None:
             return
-        halo = getattr(self, "_halo", None)
+        halo = self._halo
         if not ok:
             # fit() is raising: the peers may sit in a collective this rank never
             # enters (the ELBO all_reduce, agree()), so no barrier here, and a
@@ -214,7 +216,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
             halo.quiesce(self._engine)
 
     def _terms(self):
-        return self._ensure_engine().terms(speculate=getattr(self, "_spec_next", 0))
+        return self._ensure_engine().terms(speculate=self._spec_next)
 
     def _compute_elbo(self):
         # the reference returns a 0-d fp32 tensor (python float + fp32 tensors)
@@ -334,7 +336,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         eng, x, cov, _ = self._state(smoothed)
         sums, _ = eng.predict(x, cov, Yt=eng.Yt, include_noise=include_noise,
                               zsq=zsq, csq=csq)
-        if getattr(self, "_halo", None) is not None:
+        if self._halo is not None:
             sums = self._halo.gather_time(sums.unsqueeze(0), 1)[0]
         return self._check_dict(sums, levels)
 
@@ -358,7 +360,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         holds compute_mean's means and NaN second moments.  smoothed=True: of the
         smoothed state (:meth:`smooth`)."""
         eng, x, cov, _ = self._state(smoothed)
-        if getattr(self, "_halo", None) is not None:
+        if self._halo is not None:
             raise NotImplementedError("predict_dyads is not available on a time-sharded run: "
                                       "score with predictive_check, or fit on one process")
         t0, t1 = self._range(times, self.T, "times")
@@ -369,7 +371,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
             eng, x, cov, _ = self._state(True)
             return eng, eng.forecast_states(x[-1], cov[-1], n_steps)
         eng = self._predict_engine()
-        if getattr(self, "_halo", None) is None:
+        if self._halo is None:
             m, S = eng.x_a[-1], eng.cov[-1]
         else:   # collective getters: every rank reads the last slice and computes the same
             m, S = self.X_mean[:, -1], self.X_cov[:, -1]
@@ -424,7 +426,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
             return mstep.combine(state, dyad, cross=sm.d_lag_sum)
         eng = self._predict_engine()
         state, dyad = eng.mstep_stats()
-        if getattr(self, "_halo", None) is not None:
+        if self._halo is not None:
             state = self._halo.gather_time(state.unsqueeze(0), 1)[0]
             dyad = self._halo.gather_time(dyad.unsqueeze(0), 1)[0]
         return mstep.combine(state, dyad)

@@ -121,6 +121,29 @@ def test_no_side_effects(gpu_device):
         assert torch.equal(a, b)
 
 
+def test_side_calls_share_one_scratch(gpu_device):
+    """predictive_check, m_step_statistics(smoothed=True), smooth and
+    predictive_check again on ONE fitted object (n=48, T=6, r=3): the calls
+    share the engine's one grow-only scratch buffer, and every result has the
+    bits of the same call made first on a fresh twin."""
+    def fitted():
+        vi = _vi_of(SR.make_case((48, 6, 3), "gen"))
+        vi.fit(max_iter=2, tolerance=0.0, verbose=False)
+        return vi
+
+    calls = (("predictive_check", lambda v: v.predictive_check()),
+             ("m_step_statistics", lambda v: v.m_step_statistics(smoothed=True)),
+             ("smooth", lambda v: _arrays(v.smooth())),
+             ("predictive_check again", lambda v: v.predictive_check()))
+    vi = fitted()
+    for name, call in calls:
+        got, want = call(vi), call(fitted())
+        assert set(got) == set(want) and len(got) >= 4, name
+        for k in want:
+            a, b = np.asarray(got[k]), np.asarray(want[k])
+            assert a.dtype == b.dtype and np.array_equal(a, b), (name, k)
+
+
 def test_smoothed_interfaces(gpu_device):
     import torch
     import predictive_ref as PR
