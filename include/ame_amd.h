@@ -36,6 +36,9 @@
  *                     Gaussian posterior across time given the other nodes'
  *                     means (block-tridiagonal solve): smoothed means, marginal
  *                     covariances and lag-one cross-covariances.
+ *   ame_covar_stats,  replace nothing in the reference: the regression on dyadic
+ *   ame_covar_resid   covariates (all-pairs sums for the closed-form M-step of
+ *                     beta; the residual network every other entry point reads).
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -454,6 +457,47 @@ long long ame_smooth_work_size(const ame_dims* dims, int nodes);
 /* Dynamic LDS bytes of the solve workgroup at latent dim r (four d x (d+1) fp64
  * matrices and six d-vectors), -1 for an r that is not compiled in. */
 long long ame_smooth_lds_bytes(int r);
+
+/* ---- dyadic covariates ---------------------------------------------------------
+ * Replaces nothing the reference computes: it has no regression term.  With
+ *   y_ij,t = mu_ij,t + sum_k beta_k w_k,ij,t + eps,   eps ~ N(0, R)
+ * every other entry point runs unchanged on the residual network
+ * Y~ = Y - sum_k beta_k W_k (ame_covar_resid), and the closed-form M-step for
+ * beta needs, per slice and over the upper triangle i < j with Yt[t][i][j] and
+ * Wt[k][t][i][j] as the observation 2-vectors (ame_mstep_stats' convention),
+ *   G[k][a][b]    = sum_{i<j} w_k[a] e[b],    e = y~_ij - E[mu_ij]
+ *   H[k][l][a][b] = sum_{i<j} w_k[a] w_l[b]   (H[k][l][a][b] == H[l][k][b][a], bit for bit)
+ * ame_covar_stats: one workgroup per (slice, 64 x 64 tile of the upper triangle)
+ * forms E[mu_ij] on fp32 MFMA and e in fp32, reads each covariate tile once and
+ * adds the products w e' in fp64 (exact products of fp32 values); a second kernel
+ * adds the tile partials in tile order.  H depends on the data alone (a caller
+ * asks for it once): it has a kernel of its own over the same tiles, which sums
+ * the row blocks H[k][k..p-1] one k at a time, reading plane k from memory and
+ * planes l > k again from cache.  No atomics, no waits; a slice's row has the
+ * same bits under any split of the slices over calls (dims.t_begin / T_total /
+ * variant are only range-checked).
+ * ame_covar_resid: Yt_out = Yt_raw - sum_k beta[k] Wt[k] over the packed layout;
+ * per element s = 0, s += beta[k] * w_k for k ascending, y - s, every product and
+ * sum rounded to fp64 on its own (no FMA), one rounding to fp32.  The pad column
+ * of odd n stays what ame_pack_y wrote.  beta is p HOST doubles, read by the call. */
+#define AME_MAX_COVARIATES 8
+typedef struct ame_covar_args {
+    const float* x;      /* [T_local][n][d] means                                   */
+    const float* Yt;     /* [T_local][n][ny][2] packed residual observations        */
+    const float* Wt;     /* [p][T_local][n][ny][2], each plane packed by ame_pack_y */
+    int32_t p;           /* 1..AME_MAX_COVARIATES                                   */
+    double* G;           /* [T_local][p][2][2] fp64, or NULL                        */
+    double* H;           /* [T_local][p][p][2][2] fp64, or NULL (not both)          */
+    double* work;        /* >= ame_covar_work_size() doubles                        */
+    uint64_t work_doubles; /* size of `work` in doubles, checked                    */
+} ame_covar_args;
+int ame_covar_stats(const ame_dims* dims, const ame_covar_args* args, void* stream);
+/* Scratch doubles ame_covar_stats needs (4p + 4p^2 per tile), -1 on bad dims or p. */
+long long ame_covar_work_size(const ame_dims* dims, int p);
+/* Yt_raw, Wt and Yt_out are 16-byte aligned; Yt_out overlaps neither Yt_raw nor
+ * any plane of Wt (checked). */
+int ame_covar_resid(const ame_dims* dims, const float* Yt_raw, const float* Wt, const double* beta,
+                    int p, float* Yt_out, void* stream);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

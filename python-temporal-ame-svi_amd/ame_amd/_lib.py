@@ -93,9 +93,17 @@ class ame_smooth_args(ctypes.Structure):
                 ("work_doubles", ctypes.c_uint64)]
 
 
+AME_MAX_COVARIATES = 8
+
+
+class ame_covar_args(ctypes.Structure):
+    _fields_ = [("x", c_vp), ("Yt", c_vp), ("Wt", c_vp), ("p", c_int32), ("G", c_vp), ("H", c_vp),
+                ("work", c_vp), ("work_doubles", ctypes.c_uint64)]
+
+
 # every symbol include/ame_amd.h declares (checked by tests/test_capi.py)
 EXPORTS = ("ame_pack_y", "ame_pack_y_size", "ame_sweep", "ame_sweep_kind", "ame_sweep_work_size", "ame_sweep_orders_slices", "ame_sweep_max_slices", "ame_sweep_slice_workgroups", "ame_sweep_lds_bytes", "ame_cov",
-           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_smooth", "ame_smooth_work_size", "ame_smooth_lds_bytes", "ame_host_register", "ame_host_unregister",
+           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_smooth", "ame_smooth_work_size", "ame_smooth_lds_bytes", "ame_covar_stats", "ame_covar_work_size", "ame_covar_resid", "ame_host_register", "ame_host_unregister",
            "ame_stream_create_cu_range", "ame_stream_destroy",
            "ame_peer_alloc", "ame_peer_free", "ame_peer_open", "ame_peer_close",
            "ame_peer_probe", "ame_peer_read_u64", "ame_peer_clear",
@@ -137,6 +145,12 @@ def _declare(L):
     L.ame_smooth_work_size.restype = ctypes.c_longlong
     L.ame_smooth_lds_bytes.argtypes = [ctypes.c_int]
     L.ame_smooth_lds_bytes.restype = ctypes.c_longlong
+    L.ame_covar_stats.argtypes = [P(ame_dims), P(ame_covar_args), c_vp]
+    L.ame_covar_stats.restype = ctypes.c_int
+    L.ame_covar_work_size.argtypes = [P(ame_dims), ctypes.c_int]
+    L.ame_covar_work_size.restype = ctypes.c_longlong
+    L.ame_covar_resid.argtypes = [P(ame_dims), c_vp, c_vp, P(ctypes.c_double), ctypes.c_int, c_vp, c_vp]
+    L.ame_covar_resid.restype = ctypes.c_int
     L.ame_debug_selftest.argtypes = [c_vp, c_vp]
     L.ame_debug_selftest.restype = ctypes.c_int
     if hasattr(L, "ame_debug_occupy"):   # diagnostic; absent from older A/B builds

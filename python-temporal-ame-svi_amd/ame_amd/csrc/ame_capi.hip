@@ -34,6 +34,12 @@ long long ame_mstep_dyad_blocks(const ame_dims*);
 int ame_smooth_dispatch(const ame_dims*, const ame_smooth_args*, hipStream_t);
 long long ame_smooth_work_doubles(const ame_dims*, int nodes);
 long long ame_smooth_lds_bytes_r(int r);
+int ame_covar_stats_dispatch(const ame_dims*, const ame_covar_args*, hipStream_t);
+int ame_covar_resid_dispatch(const ame_dims*, const float* Yraw, const float* Wt, const double* beta, int p,
+                             float* out, hipStream_t);
+long long ame_covar_work_doubles(const ame_dims*, int p);
+long long ame_covar_blocks(const ame_dims*);
+long long ame_covar_plane4(const ame_dims*);
 int ame_pack_dispatch(const float*, float*, const ame_dims*, unsigned long long*, hipStream_t);
 
 static thread_local char g_err[512] = "";
@@ -470,6 +476,52 @@ int ame_mstep_stats(const ame_dims* dims, const ame_mstep_args* a, void* stream)
         return launched(ame_mstep_dyad_dispatch(dims, a, a->work + ame_mstep_state_work_doubles(dims),
                                                 (hipStream_t)stream), "mstep_dyad");
     return 0;
+}
+
+static int check_covar_p(const char* who, int p) {
+    if (p < 1 || p > AME_MAX_COVARIATES) {
+        snprintf(g_err, sizeof(g_err), "%s: p=%d covariates outside [1, %d]", who, p, AME_MAX_COVARIATES);
+        return -1;
+    }
+    return 0;
+}
+
+long long ame_covar_work_size(const ame_dims* dims, int p) {
+    if (check_dims(dims) || check_covar_p("ame_covar_work_size", p)) return -1;
+    return ame_covar_work_doubles(dims, p);
+}
+
+int ame_covar_stats(const ame_dims* dims, const ame_covar_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_covar_stats: args is NULL");
+    if (int e = check_covar_p("ame_covar_stats", a->p)) return e;
+    if (!a->x || !a->Yt || !a->Wt || !a->work) return fail("ame_covar_stats: NULL buffer (x, Yt, Wt, work)");
+    if (!a->G && !a->H) return fail("ame_covar_stats: G and H are both NULL");
+    if ((long long)a->work_doubles < ame_covar_work_doubles(dims, a->p))
+        return fail("ame_covar_stats: work holds fewer doubles than ame_covar_work_size (p=%d)", a->p);
+    if (ame_covar_blocks(dims) > 0x7FFFFFFFLL)
+        return fail("ame_covar_stats: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_covar_stats_dispatch(dims, a, (hipStream_t)stream), "covar_stats");
+}
+
+int ame_covar_resid(const ame_dims* dims, const float* Yt_raw, const float* Wt, const double* beta, int p,
+                    float* Yt_out, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (int e = check_covar_p("ame_covar_resid", p)) return e;
+    if (!Yt_raw || !Wt || !beta || !Yt_out) return fail("ame_covar_resid: NULL buffer (Yt_raw, Wt, beta, Yt_out)");
+    {   // the kernel reads and writes float4: 16-byte aligned, Yt_out apart from every input plane
+        const uintptr_t o = (uintptr_t)Yt_out, y = (uintptr_t)Yt_raw, w = (uintptr_t)Wt;
+        const uintptr_t pb = (uintptr_t)ame_covar_plane4(dims) * 16;
+        if ((o | y | w) & 15) return fail("ame_covar_resid: Yt_raw, Wt and Yt_out must be 16-byte aligned");
+        if (o < y + pb && y < o + pb) return fail("ame_covar_resid: Yt_out aliases Yt_raw");
+        if (o < w + (uintptr_t)p * pb && w < o + pb) return fail("ame_covar_resid: Yt_out aliases Wt");
+    }
+    if ((ame_covar_plane4(dims) + AME_NT - 1) / AME_NT > 0x7FFFFFFFLL)
+        return fail("ame_covar_resid: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_covar_resid_dispatch(dims, Yt_raw, Wt, beta, p, Yt_out, (hipStream_t)stream),
+                    "covar_resid");
 }
 
 long long ame_smooth_work_size(const ame_dims* dims, int nodes) {

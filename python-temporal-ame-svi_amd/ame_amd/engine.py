@@ -300,6 +300,9 @@ class DeviceEngine:
             "cuda", torch.cuda.current_device())
         self.shard = shard or Shard(0, self.T, self.T)
         self.halo = halo
+        if getattr(model, "W", None) is not None and (
+                halo is not None or self.shard.T_local != self.shard.T_total):
+            raise NotImplementedError("dyadic covariates are not available on a time-sharded run")
         self.options = opt = EngineOptions.coerce(options)
         self.lr = float(lr)
         self.C = Constants(model)
@@ -381,7 +384,105 @@ class DeviceEngine:
         # its first sweep launch, after that sweep's collectives -- a rank that
         # arrives late, as host jitter or a slow first collective makes it
         self._first_launch_delay_s = 0.0
+        # dyadic covariates (include/ame_amd.h): none -> no buffers, Yt as packed
+        self.p = 0
+        self.beta = None
+        self._covar_H = None
+        if getattr(model, "W", None) is not None:
+            self._init_covariates(model)
         self._mark_host_writes()
+
+    # ------------------------------------------------------------------
+    # dyadic covariates (ame_covar_stats / ame_covar_resid)
+    # ------------------------------------------------------------------
+    def _init_covariates(self, model):
+        """Pack the covariates W (p, n, n, T, 2) plane by plane as Y is packed,
+        keep the packed observations as Yt_raw and make Yt a separate buffer
+        holding the residual Y - sum_k beta_k W_k at the model's beta: every
+        launch keeps reading self.Yt."""
+        sh = self.shard   # the whole time axis: __init__ refused a time-sharded run
+        W = model.W.detach()
+        p = int(W.shape[0])
+        if W.dim() != 5 or tuple(W.shape[1:]) != (self.n, self.n, self.T, 2) \
+                or not 1 <= p <= _lib.AME_MAX_COVARIATES:
+            raise ValueError(f"covariates have shape {tuple(W.shape)}, expected (p, {self.n}, {self.n}, "
+                             f"{self.T}, 2) with 1 <= p <= {_lib.AME_MAX_COVARIATES}")
+        with torch.cuda.device(self.dev):
+            self.Wt = torch.empty(p, sh.T_local, self.n, self.ny, 2, dtype=torch.float32, device=self.dev)
+            mm = torch.zeros(1, dtype=torch.int64, device=self.dev)
+            for k in range(p):
+                src = W[k].float().to(self.dev).contiguous()
+                _lib.check(self.L.ame_pack_y(_ptr(src), _ptr(self.Wt[k]), ctypes.byref(self.dims),
+                                             _ptr(mm), self._sp()), "ame_pack_y")
+                del src
+            # the residual is swap-consistent when Y and every covariate are
+            self.swap_consistent = self.swap_consistent and int(mm.item()) == 0
+            self.Yt_raw = self.Yt
+            self.Yt = torch.empty_like(self.Yt_raw)
+        self.p = p
+        self.set_beta(model.beta)
+
+    def set_beta(self, beta):
+        """Rebuild the residual Yt = Yt_raw - sum_k beta_k Wt[k] (ame_covar_resid)
+        from the raw observations -- never incrementally, so nothing drifts --
+        ordered after any dropped speculative sweep."""
+        if not self.p:
+            raise ValueError("set_beta: the model has no covariates")
+        b = [float(v) for v in torch.as_tensor(beta).detach().double().flatten().tolist()]
+        if len(b) != self.p:
+            raise ValueError(f"beta has {len(b)} entries, expected {self.p}")
+        self.discard_speculation()
+        cb = (ctypes.c_double * self.p)(*b)
+        _lib.check(self.L.ame_covar_resid(ctypes.byref(self.dims), _ptr(self.Yt_raw), _ptr(self.Wt), cb,
+                                          self.p, _ptr(self.Yt), self._sp()), "ame_covar_resid")
+        self.beta = torch.tensor(b, dtype=torch.float64)
+        self._mark_host_writes()
+        self.invalidate()
+
+    def covar_stats(self, x=None):
+        """Per-slice covariate statistics of the current means (or the given
+        [T_local][n][d] means) against the residual Yt: ``G`` [T_local][p][2][2]
+        and ``H`` [T_local][p][p][2][2], fp64 on the device (ame_covar_stats).
+        H depends on the data alone: it is computed by the first call and kept.
+        Whole slices at a time within the scratch budget of predict(); a slice's
+        row does not depend on the split."""
+        if not self.p:
+            raise ValueError("covar_stats: the model has no covariates")
+        self.discard_speculation()
+        n, p, TL = self.n, self.p, self.shard.T_local
+        if x is None:
+            x = self.x_a
+        assert tuple(x.shape) == (TL, n, self.d) and x.is_contiguous()
+
+        def ame_covar_work_size(dm):   # the one-argument query _slice_chunk takes, at this p
+            return self.L.ame_covar_work_size(dm, p)
+
+        chunk, wk = self._slice_chunk(ame_covar_work_size, TL)
+        want_h = self._covar_H is None
+        with torch.cuda.device(self.dev):
+            G = torch.empty(TL, p, 2, 2, dtype=torch.float64, device=self.dev)
+            H = torch.empty(TL, p, p, 2, 2, dtype=torch.float64, device=self.dev) if want_h else None
+            # the p planes of a slice range are not contiguous: a chunked call gets a
+            # copy, made on the main stream before the ELBO stream is ordered after it
+            wparts = [self.Wt if chunk >= TL else self.Wt[:, s0:min(TL, s0 + chunk)].contiguous()
+                      for s0 in range(0, TL, chunk)]
+        with self._elbo_call("covar") as sp:
+            for c, s0 in enumerate(range(0, TL, chunk)):
+                s1 = min(TL, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, self.shard.t_begin + s0, self.shard.T_total,
+                                   self.vcode)
+                a = _lib.ame_covar_args(
+                    x=_ptr(x[s0:s1]), Yt=_ptr(self.Yt[s0:s1]), Wt=_ptr(wparts[c]), p=p,
+                    G=_ptr(G[s0:s1]), H=_ptr(H[s0:s1]) if want_h else None, work=_ptr(wk),
+                    work_doubles=wk.numel())
+                _lib.check(self.L.ame_covar_stats(ctypes.byref(dm), ctypes.byref(a), sp),
+                           "ame_covar_stats")
+        for t in (x, self.Yt, self.Wt, wk, G, *wparts):
+            t.record_stream(self._elbo_stream())
+        if want_h:
+            H.record_stream(self._elbo_stream())
+            self._covar_H = H
+        return G, self._covar_H
 
     def _cu_stream(self, first, num, slot=0):
         """A stream over compute units [first, first + num) (C-ABI, HIP CU mask),

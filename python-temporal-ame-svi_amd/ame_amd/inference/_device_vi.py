@@ -354,7 +354,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
     def predict_dyads(self, times, rows=None, cols=None, include_noise=True, max_elements=2 ** 27,
                       smoothed=False):
         """Dense predictive moments ``(mean, second)`` on the CPU: (ni, nj, S, 2)
-        = E[mu_ij] and (ni, nj, S, 3) = Var of entry 0, Var of entry 1 and their
+        = E[mu_ij] (plus sum_k beta_k w_k,ij when the model has covariates) and (ni, nj, S, 3) = Var of entry 0, Var of entry 1 and their
         covariance (with model.R added when include_noise).  ``times`` is an int
         or a slice, ``rows`` / ``cols`` contiguous ranges or slices.  The diagonal
         holds compute_mean's means and NaN second moments.  smoothed=True: of the
@@ -364,7 +364,34 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
             raise NotImplementedError("predict_dyads is not available on a time-sharded run: "
                                       "score with predictive_check, or fit on one process")
         t0, t1 = self._range(times, self.T, "times")
-        return self._dense(eng, x[t0:t1], cov[t0:t1], rows, cols, include_noise, max_elements)
+        mean, second = self._dense(eng, x[t0:t1], cov[t0:t1], rows, cols, include_noise, max_elements)
+        if getattr(self.model, "W", None) is not None:
+            mean = mean + self._covariate_block(self.model.W[:, :, :, t0:t1], rows, cols)
+        return mean, second
+
+    def _covariate_block(self, W, rows, cols):
+        """sum_k beta_k W_k of the block rows x cols, (ni, nj, S, 2) fp32 on the CPU."""
+        i0, i1 = self._range(rows, self.n, "rows")
+        j0, j1 = self._range(cols, self.n, "cols")
+        return self.model.covariate_effect(W[:, i0:i1, j0:j1].to("cpu"))
+
+    def _future_covariates(self, W_future, h):
+        """The (p, n, n, h, 2) covariates of held-out steps: required exactly when
+        the model has covariates (None otherwise)."""
+        W = getattr(self.model, "W", None)
+        if W is None:
+            if W_future is not None:
+                raise ValueError("W_future given but the model has no covariates")
+            return None
+        if W_future is None:
+            raise ValueError("the model has covariates: W_future (p, n, n, h, 2) is required")
+        Wf = torch.as_tensor(W_future, dtype=torch.float32)
+        if Wf.dim() == 4:
+            Wf = Wf.unsqueeze(0)
+        want = (int(W.shape[0]), self.n, self.n, int(h), 2)
+        if tuple(Wf.shape) != want:
+            raise ValueError(f"W_future has shape {tuple(Wf.shape)}, expected {want}")
+        return Wf
 
     def _forecast_states(self, n_steps, smoothed=False):
         if smoothed:   # the smoothed last slice is the filtered one
@@ -387,11 +414,16 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         return m.permute(1, 0, 2).to("cpu").contiguous(), S.permute(1, 0, 2, 3).to("cpu").contiguous()
 
     def forecast_check(self, Y_future, levels=(0.5, 0.9, 0.95), include_noise=True,
-                       smoothed=False) -> dict:
+                       smoothed=False, W_future=None) -> dict:
         """predictive_check of held-out steps: ``Y_future`` (n, n, h, 2) scored
-        against the h-step forecast; the same dictionary, of length h."""
+        against the h-step forecast; the same dictionary, of length h.  A model
+        with covariates needs theirs for those steps, ``W_future`` (p, n, n, h,
+        2): the residual Y_future - sum_k beta_k W_future[k] is scored."""
         levels, zsq, csq = self._thresholds(levels)
         Y_future = torch.as_tensor(Y_future)
+        Wf = self._future_covariates(W_future, Y_future.shape[2] if Y_future.dim() == 4 else 1)
+        if Wf is not None:
+            Y_future = Y_future.to("cpu", torch.float32) - self.model.covariate_effect(Wf)
         eng, (m, S) = self._forecast_states(int(Y_future.shape[2]) if Y_future.dim() == 4 else 1,
                                             smoothed)
         Yt = eng.pack_future(Y_future)
@@ -399,10 +431,16 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         return self._check_dict(sums, levels)
 
     def forecast_dyads(self, n_steps: int = 1, rows=None, cols=None, include_noise=True,
-                       max_elements=2 ** 27, smoothed=False):
-        """predict_dyads of the h-step forecast: (ni, nj, h, 2) and (ni, nj, h, 3)."""
+                       max_elements=2 ** 27, smoothed=False, W_future=None):
+        """predict_dyads of the h-step forecast: (ni, nj, h, 2) and (ni, nj, h, 3).
+        A model with covariates needs ``W_future`` (p, n, n, h, 2); sum_k beta_k
+        W_future[k] of the block is added to the means."""
+        Wf = self._future_covariates(W_future, n_steps)
         eng, (m, S) = self._forecast_states(n_steps, smoothed)
-        return self._dense(eng, m, S, rows, cols, include_noise, max_elements)
+        mean, second = self._dense(eng, m, S, rows, cols, include_noise, max_elements)
+        if Wf is not None:
+            mean = mean + self._covariate_block(Wf, rows, cols)
+        return mean, second
 
     # ---------------- variational EM: learn Phi, Q, R, Sigma, Psi (extension) ----------------
     # The reference never estimates the model parameters.  The E-step is the
@@ -423,18 +461,27 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         if smoothed:
             eng, x, cov, sm = self._state(True)
             state, dyad = eng.mstep_stats(x, cov)
-            return mstep.combine(state, dyad, cross=sm.d_lag_sum)
+            stats = mstep.combine(state, dyad, cross=sm.d_lag_sum)
+            if eng.p:
+                stats.update(mstep.combine_covar(*eng.covar_stats(x), eng.beta))
+            return stats
         eng = self._predict_engine()
         state, dyad = eng.mstep_stats()
         if self._halo is not None:
             state = self._halo.gather_time(state.unsqueeze(0), 1)[0]
             dyad = self._halo.gather_time(dyad.unsqueeze(0), 1)[0]
-        return mstep.combine(state, dyad)
+        stats = mstep.combine(state, dyad)
+        if eng.p:   # covariates: G, H and the beta the residual Yt was taken at
+            stats.update(mstep.combine_covar(*eng.covar_stats(), eng.beta))
+        return stats
 
     def _model_params64(self) -> dict:
         m = self.model
-        return {k: getattr(m, k).detach().to("cpu", torch.float64).clone()
-                for k in ("Phi", "Q", "R", "Sigma", "Psi")}
+        out = {k: getattr(m, k).detach().to("cpu", torch.float64).clone()
+               for k in ("Phi", "Q", "R", "Sigma", "Psi")}
+        if getattr(m, "W", None) is not None:
+            out["beta"] = m.beta.detach().to("cpu", torch.float64).clone()
+        return out
 
     def m_step(self, update=("Phi", "Q", "R", "Sigma0"), phi_structure="full", apply=True,
                smoothed=False) -> dict:
@@ -446,8 +493,17 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         evaluation error is a small multiple of 2^-52 of that).  ``apply`` writes them to the model as fp32 (``R_inv``
         with ``R``) and rebuilds the engine's constants from those attributes,
         as a fresh VI on the updated model would.  A non-finite or
-        non-positive-definite result raises ValueError and applies nothing."""
+        non-positive-definite result raises ValueError and applies nothing.
+        With covariates (model.set_covariates) ``update`` may name "beta": the
+        regression coefficients get their closed-form step first and R is then
+        taken at the new beta; the statistics carry ``G``, ``H`` and the ``beta``
+        they were taken at, the result ``beta``.  Applying writes ``model.beta``
+        (fp32) and rebuilds the engine's residual network.  A singular system
+        for beta raises ValueError and applies nothing."""
         from .. import mstep
+        update = tuple(update)
+        if "beta" in update and getattr(self.model, "W", None) is None:
+            raise ValueError('update has "beta" but the model has no covariates (set_covariates)')
         stats = self.m_step_statistics(smoothed=smoothed)
         old = self._model_params64()
         new = mstep.solve(stats, old, self.n, self.T, update, phi_structure)
@@ -460,13 +516,16 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         out["objective_scale"] = mstep.objective_scale(stats, new, self.n, self.T)
         if apply:
             m = self.model
-            changed = {"Phi": ("Phi",), "Q": ("Q",), "R": ("R",), "Sigma0": ("Sigma", "Psi")}
+            changed = {"Phi": ("Phi",), "Q": ("Q",), "R": ("R",), "Sigma0": ("Sigma", "Psi"),
+                       "beta": ("beta",)}
             for u in update:
                 for k in changed[u]:
                     setattr(m, k, new32[k])
             if "R" in update:
                 m.R_inv = torch.linalg.inv(m.R)
             self._ensure_engine().set_constants(m)
+            if "beta" in update:   # the residual network every kernel reads, at the new beta
+                self._engine.set_beta(m.beta)
         return out
 
     def fit_em(self, n_rounds: int = 10, inner_iter: int = 10,

@@ -104,6 +104,49 @@ class TemporalAMEModel:
         self.M = None
         self.X: Optional[torch.Tensor] = None
         self.Y: Optional[torch.Tensor] = None
+        # dyadic covariates (extension, set_covariates): none by default
+        self.W: Optional[torch.Tensor] = None
+        self.beta: Optional[torch.Tensor] = None
+
+    MAX_COVARIATES = 8   # AME_MAX_COVARIATES of include/ame_amd.h
+
+    def set_covariates(self, W, beta=None) -> None:
+        """Dyadic covariates of the regression term y_ij = beta . w_ij + a_i + b_j
+        + u_i . v_j + eps (the reference has none).  ``W`` is (p, n, n, T, 2) or
+        (n, n, T, 2) in Y's layout per covariate, W[k, i, j, t] = (w_k,ij, w_k,ji);
+        ``beta`` (p,) defaults to zeros and is stored as fp32 ``model.beta``.
+        Set them before data is generated (the generators then add sum_k beta_k
+        W_k to Y) and before a VI object is built on the model."""
+        W = torch.as_tensor(W)
+        if W.dim() == 4:
+            W = W.unsqueeze(0)
+        if W.dim() != 5 or tuple(W.shape[1:]) != (self.n, self.n, self.T, 2):
+            raise ValueError(f"W has shape {tuple(W.shape)}, expected (p, {self.n}, {self.n}, "
+                             f"{self.T}, 2) or ({self.n}, {self.n}, {self.T}, 2)")
+        p = int(W.shape[0])
+        if not 1 <= p <= self.MAX_COVARIATES:
+            raise ValueError(f"{p} covariates: between 1 and {self.MAX_COVARIATES} are supported")
+        if not bool(torch.isfinite(W).all()):
+            raise ValueError("W holds non-finite values")
+        if beta is None:
+            b = torch.zeros(p, dtype=torch.float32)
+        else:
+            b = torch.as_tensor(beta).detach().to("cpu", torch.float32).flatten().clone()
+            if b.numel() != p:
+                raise ValueError(f"beta has {b.numel()} entries, expected {p}")
+            if not bool(torch.isfinite(b).all()):
+                raise ValueError("beta holds non-finite values")
+        self.W = W.detach().to(torch.float32).contiguous()
+        self.beta = b
+
+    def covariate_effect(self, W=None, beta=None) -> torch.Tensor:
+        """sum_k beta_k W_k, (n, n, S, 2) fp32, of the model's covariates or of a
+        given (p, n, n, S, 2) stack (future steps)."""
+        if self.W is None:
+            raise ValueError("the model has no covariates")
+        W = self.W if W is None else torch.as_tensor(W, dtype=torch.float32)
+        b = (self.beta if beta is None else torch.as_tensor(beta)).to(W.device, torch.float32)
+        return torch.einsum("k,kijtc->ijtc", b, W)
 
     # temporal_ame.py:129-145
     def _initialize_dynamics(self) -> None:
@@ -180,6 +223,8 @@ class TemporalAMEModel:
             self.Y[iu[0], iu[1], t] = dy
             self.Y[iu[1], iu[0], t, 0] = dy[:, 1]
             self.Y[iu[1], iu[0], t, 1] = dy[:, 0]
+        if self.W is not None:   # without covariates the reference's bits, untouched
+            self.Y = self.Y + self.covariate_effect()
         if return_latents:
             return self.Y, self.X
         return self.Y
@@ -228,6 +273,8 @@ class TemporalAMEModel:
             Yt[iu[1], iu[0], 0] = dy[iu[0], iu[1], 1]
             Yt[iu[1], iu[0], 1] = dy[iu[0], iu[1], 0]
             Y[:, :, t] = Yt
+        if self.W is not None:
+            Y = Y + self.covariate_effect(self.W.to(dev))
         self.X, self.Y = X, Y
         if return_latents:
             return Y, X

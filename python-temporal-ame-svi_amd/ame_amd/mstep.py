@@ -27,8 +27,66 @@ from __future__ import annotations
 
 import torch
 
-UPDATES = ("Phi", "Q", "R", "Sigma0")
+UPDATES = ("Phi", "Q", "R", "Sigma0", "beta")
+DEFAULT_UPDATE = ("Phi", "Q", "R", "Sigma0")   # "beta" only on request: it needs covariates
 PHI_STRUCTURES = ("full", "scalar")
+
+# Dyadic covariates (ame_covar_stats): y_ij = mu_ij + sum_k beta_k w_k,ij + eps.
+# The statistics are taken on the residual y~ = y - sum_k beta_k w_k at the
+# beta stored with them (stats["beta"]), e = y~ - E[mu]:
+#     G[k] = sum w_k e'   (p, 2, 2)        H[k][l] = sum w_k w_l'   (p, p, 2, 2)
+# and Rss at beta + delta is Rss - sum_k delta_k (G_k + G_k') + sum_kl delta_k
+# delta_l H[k][l], so the R-term of F is maximised over beta, at fixed R, by
+#     (sum_ab Rinv[a][b] H[k][l][a][b]) delta = sum_ab Rinv[a][b] G[k][a][b].
+# With "beta" and "R" both updated the step is beta first, then R = Rss(beta_new)
+# / pairs: a conditional-maximisation step, each half cannot lower F.
+
+
+def combine_covar(G: torch.Tensor, H: torch.Tensor, beta) -> dict:
+    """Per-slice rows G (T, p, 2, 2) and H (T, p, p, 2, 2) -> their sums, slice
+    by slice in time order as :func:`combine` adds its rows, with the beta the
+    residual was taken at."""
+    G = G.to("cpu", torch.float64)
+    H = H.to("cpu", torch.float64)
+    g = torch.zeros(G.shape[1:], dtype=torch.float64)
+    h = torch.zeros(H.shape[1:], dtype=torch.float64)
+    for t in range(int(G.shape[0])):
+        g += G[t]
+        h += H[t]
+    return {"G": g, "H": h, "beta": torch.as_tensor(beta).detach().to("cpu", torch.float64).clone()}
+
+
+def rss_at(stats: dict, delta: torch.Tensor) -> torch.Tensor:
+    """Rss at stats["beta"] + delta."""
+    G, H = stats["G"], stats["H"]
+    Rss = stats["Rss"] - torch.einsum("k,kab->ab", delta, G + G.transpose(1, 2))
+    return Rss + torch.einsum("k,l,klab->ab", delta, delta, H)
+
+
+def _rss_for(stats: dict, params: dict) -> torch.Tensor:
+    """Rss at params["beta"] (the statistics' own Rss without covariates)."""
+    if "G" not in stats or "beta" not in params:
+        return stats["Rss"]
+    delta = params["beta"] - stats["beta"]
+    if not bool(delta.any()):
+        return stats["Rss"]
+    return rss_at(stats, delta)
+
+
+def beta_step(stats: dict, R: torch.Tensor) -> torch.Tensor:
+    """delta maximising the R-term of F over beta at fixed R; a singular system
+    (collinear covariates) raises ValueError."""
+    if "G" not in stats or "H" not in stats:
+        raise ValueError('"beta" needs the covariate statistics G and H: the model has no covariates')
+    Ri = _sym(torch.linalg.inv(R))
+    A = _sym(torch.einsum("ab,klab->kl", Ri, stats["H"]))
+    b = torch.einsum("ab,kab->k", Ri, stats["G"])
+    _, info = torch.linalg.cholesky_ex(A)
+    scale = A.diagonal().abs().max()
+    if int(info) != 0 or not bool(torch.isfinite(A).all()) \
+            or float(torch.linalg.eigvalsh(A)[0]) <= 2.0 ** -40 * float(scale):
+        raise ValueError("M-step: the system for beta is singular (collinear or zero covariates)")
+    return torch.linalg.solve(A, b)
 
 
 def combine(state: torch.Tensor, dyad: torch.Tensor, cross=None) -> dict:
@@ -74,10 +132,12 @@ def transition_scatter(stats, Phi):
 
 
 def objective(stats: dict, params: dict, n: int, T: int) -> float:
-    """F(theta) above; params holds fp64 Phi, Q, R, Sigma, Psi."""
+    """F(theta) above; params holds fp64 Phi, Q, R, Sigma, Psi and, with
+    covariate statistics G, H in `stats`, optionally beta (Rss is then taken at
+    that beta)."""
     R, Q = params["R"], params["Q"]
     S0 = blockdiag(params["Sigma"], params["Psi"])
-    f = -0.5 * (stats["pairs"] * torch.logdet(R) + torch.trace(torch.linalg.solve(R, stats["Rss"])))
+    f = -0.5 * (stats["pairs"] * torch.logdet(R) + torch.trace(torch.linalg.solve(R, _rss_for(stats, params))))
     f = f - 0.5 * (n * torch.logdet(S0) + torch.trace(torch.linalg.solve(S0, stats["A0"])))
     if T > 1:
         M = transition_scatter(stats, params["Phi"])
@@ -91,6 +151,11 @@ def objective_scale(stats: dict, params: dict, n: int, T: int) -> float:
     R, Q = params["R"], params["Q"]
     S0 = blockdiag(params["Sigma"], params["Psi"])
     m = abs(stats["pairs"] * torch.logdet(R)) + (torch.linalg.inv(R) * stats["Rss"]).abs().sum()
+    if "G" in stats and "beta" in params:   # the terms Rss at params["beta"] is made of
+        dl = (params["beta"] - stats["beta"]).abs()
+        G, H = stats["G"].abs(), stats["H"].abs()
+        extra = torch.einsum("k,kab->ab", dl, G + G.transpose(1, 2)) + torch.einsum("k,l,klab->ab", dl, dl, H)
+        m = m + (torch.linalg.inv(R).abs() * extra).sum()
     m = m + abs(n * torch.logdet(S0)) + (torch.linalg.inv(S0) * stats["A0"]).abs().sum()
     if T > 1:
         Phi, A10, A00 = params["Phi"], stats["A10"], stats["A00"]
@@ -105,9 +170,11 @@ def _sym(a):
     return 0.5 * (a + a.T)
 
 
-def solve(stats: dict, params: dict, n: int, T: int, update=UPDATES, phi_structure="full") -> dict:
+def solve(stats: dict, params: dict, n: int, T: int, update=DEFAULT_UPDATE, phi_structure="full") -> dict:
     """New fp64 parameters: those named in `update` at their maximisers (Q with
-    the Phi just chosen), the others as in `params`."""
+    the Phi just chosen; R with the beta just chosen), the others as in
+    `params`.  "beta" needs the covariate statistics (G, H, beta) in `stats`;
+    the result then has a "beta" entry as well."""
     update = tuple(update)
     bad = set(update) - set(UPDATES)
     if bad:
@@ -127,8 +194,16 @@ def solve(stats: dict, params: dict, n: int, T: int, update=UPDATES, phi_structu
             new["Phi"] = phi * torch.eye(d, dtype=torch.float64)
     if "Q" in update:
         new["Q"] = _sym(transition_scatter(stats, new["Phi"])) / (n * (T - 1))
+    Rss = stats["Rss"]
+    if "beta" in params:
+        new["beta"] = params["beta"].clone()
+        Rss = _rss_for(stats, params)
+    if "beta" in update:
+        delta = beta_step(stats, params["R"])
+        new["beta"] = stats["beta"] + delta
+        Rss = rss_at(stats, delta)
     if "R" in update:
-        new["R"] = stats["Rss"] / stats["pairs"]
+        new["R"] = Rss / stats["pairs"]
     if "Sigma0" in update:
         new["Sigma"] = _sym(stats["A0"][:2, :2]) / n
         new["Psi"] = _sym(stats["A0"][2:, 2:]) / n

@@ -1,0 +1,209 @@
+"""The covariate M-step on the host (ame_amd/mstep.py) against the fp64 numpy
+reference tests/covar_ref.py, the identities it rests on, and the model's
+set_covariates.  No GPU.
+
+Bounds.
+  F is evaluated in fp64 from a few dozen terms: a step that cannot lower F may
+  show a decrease of a few roundings of the sum of its |terms|, so "does not
+  decrease" allows 4 x 2^-52 x objective_scale.
+  Rss(beta_new) from the identity and Rss recomputed from the residuals at
+  beta_new are both fp64 sums over the same N dyads of terms whose magnitudes
+  add up to Sigma = sum(|e e'| + |V|) + sum_k |delta_k| (|G_k| + |G_k'|)-summands +
+  sum_kl |delta_k delta_l| |H_kl|-summands: they differ by re-association and by
+  the rounding of each expanded product, within N 2^-52 Sigma (N >= 28 dyads here,
+  against a handful of roundings per summand).
+"""
+import numpy as np
+import pytest
+import torch
+
+import covar_ref as CR
+import mstep_ref as M
+import predictive_ref as PR
+
+EPS = 2.0 ** -52
+
+
+def _case(n=12, T=3, r=2, p=3, seed=0):
+    """A random state, covariates, a network with a covariate effect, and the
+    statistics at a starting beta, as numpy (reference) and torch (mstep.py)."""
+    rng = np.random.default_rng(100 + seed)
+    X, S = PR.make_state(n, T, r, seed=seed)
+    W = CR.make_w(n, T, p, seed=seed)
+    beta_true = rng.standard_normal(p)
+    Y = np.zeros((n, n, T, 2))
+    for t in range(T):
+        Y[:, :, t] = CR.mean_mu(X[:, t], r)
+    Y = Y + CR.effect(W, beta_true) + 0.3 * rng.standard_normal(Y.shape)
+    beta0 = 0.5 * rng.standard_normal(p)
+    Yres = Y - CR.effect(W, beta0)
+    st = CR.statistics(X, S, r, Yres, W, beta0)
+    d = 2 + 2 * r
+    A = rng.standard_normal((2, 2))
+    params = dict(Phi=0.7 * np.eye(d), Q=0.2 * np.eye(d), R=A @ A.T + 0.5 * np.eye(2),
+                  Sigma=np.eye(2), Psi=np.eye(2 * r), beta=beta0.copy())
+    return dict(n=n, T=T, r=r, p=p, X=X, S=S, W=W, Y=Y, st=st, params=params)
+
+
+def _t(dct):
+    return {k: (torch.from_numpy(np.array(v, dtype=np.float64)) if isinstance(v, np.ndarray) else v)
+            for k, v in dct.items()}
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_solve_matches_reference_and_maximises_F(seed):
+    from ame_amd import mstep
+    c = _case(seed=seed, p=1 + seed)
+    st, pr, n, T = _t(c["st"]), _t(c["params"]), c["n"], c["T"]
+    new = mstep.solve(st, pr, n, T, update=("beta",))
+    ref = CR.m_step(c["st"], c["params"], n, T, update=("beta",))
+    assert np.allclose(new["beta"].numpy(), ref["beta"], rtol=1e-12, atol=0)
+    for k in M.PARAMS:
+        assert torch.equal(new[k], pr[k]), k
+    f_new = mstep.objective(st, new, n, T)
+    assert abs(f_new - CR.objective(c["st"], ref, n, T)) <= 64 * EPS * mstep.objective_scale(st, new, n, T)
+    rng = np.random.default_rng(seed)
+    for scale in (1e-6, 1e-3, 1e-1, 1.0):
+        pert = dict(new, beta=new["beta"] + scale * torch.from_numpy(rng.standard_normal(c["p"])))
+        assert f_new >= mstep.objective(st, pert, n, T), scale
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_beta_then_R_does_not_lower_F(seed):
+    from ame_amd import mstep
+    c = _case(seed=seed)
+    st, pr, n, T = _t(c["st"]), _t(c["params"]), c["n"], c["T"]
+    before = mstep.objective(st, pr, n, T)
+    half = mstep.solve(st, pr, n, T, update=("beta",))
+    new = mstep.solve(st, pr, n, T, update=("beta", "R"))
+    assert torch.equal(half["beta"], new["beta"])
+    slack = 4 * EPS * mstep.objective_scale(st, new, n, T)
+    f_half, f_new = mstep.objective(st, half, n, T), mstep.objective(st, new, n, T)
+    print(f"F {before:.6f} -> {f_half:.6f} (beta) -> {f_new:.6f} (beta, R); slack {slack:.2e}")
+    assert f_half >= before - slack and f_new >= f_half - slack and f_new >= before - slack
+    # R is Rss at the new beta over the pairs
+    ref = CR.m_step(c["st"], c["params"], n, T, update=("beta", "R"))
+    assert np.allclose(new["R"].numpy(), ref["R"], rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_rss_identity_equals_recomputed_residuals(seed):
+    from ame_amd import mstep
+    c = _case(seed=seed)
+    st, pr, n, T, r = _t(c["st"]), _t(c["params"]), c["n"], c["T"], c["r"]
+    delta = mstep.beta_step(st, pr["R"])
+    got = mstep.rss_at(st, delta).numpy()
+    beta_new = c["st"]["beta"] + delta.numpy()
+    Yres = c["Y"] - CR.effect(c["W"], beta_new)
+    want = M.statistics(c["X"], c["S"], r, Yres)["Rss"]
+    # Sigma: the |summands| of the identity's three parts, per entry of Rss
+    dmag = M.dyad_rows(c["X"], c["S"], r, c["Y"] - CR.effect(c["W"], c["st"]["beta"]))[1].sum(0)
+    _, Gm, _, Hm = CR.gh_rows(c["X"], r, c["Y"] - CR.effect(c["W"], c["st"]["beta"]), c["W"])
+    Gm, Hm, ad = Gm.sum(0), Hm.sum(0), np.abs(delta.numpy())
+    sig = (np.array([[dmag[1], dmag[3]], [dmag[3], dmag[2]]])
+           + np.einsum("k,kab->ab", ad, Gm + np.swapaxes(Gm, 1, 2)) + np.einsum("k,l,klab->ab", ad, ad, Hm))
+    N = T * n * (n - 1) // 2
+    err = np.abs(got - want)
+    print(f"max err / (N 2^-52 Sigma) = {(err / (N * EPS * sig)).max():.3e}")
+    assert (err <= N * EPS * sig).all()
+
+
+def test_solve_without_beta_is_unchanged():
+    """Without "beta" in update, and without covariate statistics, solve,
+    objective and objective_scale give what the plain formulas give."""
+    from ame_amd import mstep
+    c = _case()
+    plain_st = {k: v for k, v in c["st"].items() if k not in ("G", "H", "beta")}
+    plain_pr = {k: v for k, v in c["params"].items() if k != "beta"}
+    st, pr = _t(plain_st), _t(plain_pr)
+    new = mstep.solve(st, pr, c["n"], c["T"])
+    ref = M.m_step(plain_st, plain_pr, c["n"], c["T"])
+    assert set(new) == set(M.PARAMS)
+    for k in M.PARAMS:
+        assert np.allclose(new[k].numpy(), ref[k], rtol=1e-12, atol=1e-300), k
+    assert torch.equal(new["R"], st["Rss"] / st["pairs"])
+    assert mstep.objective(st, pr, c["n"], c["T"]) == pytest.approx(M.objective(plain_st, plain_pr, c["n"], c["T"]), rel=1e-13)
+    # with the covariate statistics present but "beta" not updated: the same, beta carried
+    full = mstep.solve(_t(c["st"]), _t(c["params"]), c["n"], c["T"], update=("Phi", "Q", "R", "Sigma0"))
+    for k in M.PARAMS:
+        assert torch.equal(full[k], new[k]), k
+    assert torch.equal(full["beta"], _t(c["params"])["beta"])
+    with pytest.raises(ValueError):
+        mstep.solve(st, pr, c["n"], c["T"], update=("beta",))      # no G / H
+
+
+def test_singular_beta_system_raises():
+    from ame_amd import mstep
+    c = _case(p=2)
+    W = c["W"].copy()
+    W[1] = 2.0 * W[0]                                             # collinear covariates
+    beta0 = c["st"]["beta"]
+    st = _t(CR.statistics(c["X"], c["S"], c["r"], c["Y"] - CR.effect(W, beta0), W, beta0))
+    with pytest.raises(ValueError, match="singular"):
+        mstep.solve(st, _t(c["params"]), c["n"], c["T"], update=("beta", "R"))
+
+
+def test_set_covariates_shapes_and_errors():
+    from ame_amd import TemporalAMEModel
+    n, T, r = 6, 3, 2
+    m = TemporalAMEModel(n, T, r, seed=1)
+    assert m.W is None and m.beta is None
+    W = torch.from_numpy(CR.make_w(n, T, 2))
+    m.set_covariates(W)
+    assert tuple(m.W.shape) == (2, n, n, T, 2) and m.W.dtype == torch.float32
+    assert m.beta.dtype == torch.float32 and torch.equal(m.beta, torch.zeros(2))
+    m.set_covariates(W[0], beta=[0.25])
+    assert tuple(m.W.shape) == (1, n, n, T, 2) and torch.equal(m.beta, torch.tensor([0.25]))
+    for bad in (W[:, :5], W[..., :1], torch.zeros(9, n, n, T, 2), torch.zeros(0, n, n, T, 2),
+                torch.zeros(n, n, T)):
+        with pytest.raises(ValueError):
+            m.set_covariates(bad)
+    with pytest.raises(ValueError):
+        m.set_covariates(W, beta=[1.0])
+    with pytest.raises(ValueError):
+        m.set_covariates(W, beta=[1.0, float("nan")])
+    Wn = W.clone()
+    Wn[0, 0, 1, 0, 0] = float("inf")
+    with pytest.raises(ValueError):
+        m.set_covariates(Wn)
+    assert tuple(m.W.shape) == (1, n, n, T, 2)                    # a refused call changes nothing
+
+
+def test_generators_add_the_effect_only_with_covariates():
+    from ame_amd import TemporalAMEModel
+    n, T, r = 7, 3, 2
+    W = torch.from_numpy(CR.make_w(n, T, 2))
+    for gen in ("generate_data", "generate_data_fast"):
+        a = TemporalAMEModel(n, T, r, seed=3)
+        Ya = getattr(a, gen)().clone()
+        b = TemporalAMEModel(n, T, r, seed=3)
+        b.set_covariates(W, beta=[0.5, -2.0])
+        Yb = getattr(b, gen)()
+        assert torch.equal(Yb, Ya + 0.5 * W[0] + -2.0 * W[1]) or torch.allclose(Yb, Ya + 0.5 * W[0] - 2.0 * W[1], rtol=0, atol=1e-6)
+        assert torch.equal(b.X, a.X)
+        z = TemporalAMEModel(n, T, r, seed=3)
+        z.set_covariates(W)
+        assert torch.equal(getattr(z, gen)(), Ya)                 # beta = 0: the same network
+
+
+def test_end_to_end_oracle_recovers_beta():
+    """Condition (c) of the GPU end-to-end test, on the fp64 oracle alone: the
+    final |beta_hat - beta|_inf < 0.5 min|beta|; F never decreases."""
+    em = CR.cpu_runs()["em64"]
+    for k, rd in enumerate(em):
+        print(f"round {k}: beta {rd['beta'].tolist()} R {rd['R'].flatten()[[0, 1, 3]].tolist()} "
+              f"F {rd['objective_before']:.4f} -> {rd['objective_after']:.4f}")
+        assert rd["objective_after"] >= rd["objective_before"] - 1e-9 * abs(rd["objective_before"])
+    err = np.abs(em[-1]["beta"] - np.array(CR.EM_BETA)).max()
+    assert err < 0.5 * np.abs(np.array(CR.EM_BETA)).min(), err
+
+
+def test_contraction_probe_separates_fused_from_unfused():
+    """The constructed element of the GPU residual test: numpy's fp64
+    multiply-then-add gives `unfused`, a fused multiply-add would give `fused`,
+    and the two are different fp32 values."""
+    w, beta, unfused, fused = CR.contraction_probe()
+    assert unfused != fused
+    Y = np.zeros((1, 1, 1, 2), dtype=np.float32)
+    W = np.broadcast_to(w[:, None, None, None, None], (2, 1, 1, 1, 2)).copy()
+    assert (CR.resid(Y, W, beta) == unfused).all()
