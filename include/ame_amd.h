@@ -39,6 +39,9 @@
  *   ame_covar_stats,  replace nothing in the reference: the regression on dyadic
  *   ame_covar_resid   covariates (all-pairs sums for the closed-form M-step of
  *                     beta; the residual network every other entry point reads).
+ *   ame_pack_mask,    replace nothing in the reference: partially observed
+ *   ame_fill_missing  networks (the packed mask of hidden pairs; the working
+ *                     network the sweep and the ELBO kernels read in their place).
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -335,6 +338,9 @@ int ame_elbo_pairs_diag(const ame_dims* dims, const ame_elbo_args* args, void* s
  * formulas rest on does not hold there). */
 #define AME_PREDICT_MAX_LEVELS 4
 #define AME_PREDICT_SUMS (9 + 3 * AME_PREDICT_MAX_LEVELS)
+/* mask_select of ame_predict_args / ame_mstep_args (missing dyads, below) */
+#define AME_MASK_OBSERVED 1
+#define AME_MASK_HIDDEN 2
 typedef struct ame_predict_args {
     const float* x;      /* [S][n][d] means              (S = dims.T_local)           */
     const float* cov;    /* [S][n][d][d] covariances                                  */
@@ -349,6 +355,10 @@ typedef struct ame_predict_args {
                             (noise included as given), or NULL                        */
     int32_t i0, i1, j0, j1;              /* dense block, ignored when dense == NULL   */
     double* work;        /* >= ame_predict_work_size() doubles                        */
+    const uint64_t* Mt;  /* [S][n][nw] packed mask (ame_pack_mask), or NULL           */
+    int32_t mask_select; /* 0: every pair; AME_MASK_OBSERVED / AME_MASK_HIDDEN: only
+                            the pairs i < j whose mask bit is 0 / 1 are scored, and
+                            sums[0] counts those (needs Mt and sums)                  */
 } ame_predict_args;
 int ame_predict(const ame_dims* dims, const ame_predict_args* args, void* stream);
 /* Scratch doubles ame_predict needs (per-node feature rows and per-workgroup
@@ -386,6 +396,9 @@ typedef struct ame_mstep_args {
     double* state;           /* [T_local][2][d][d] fp64: P_t, C_t, or NULL */
     double* dyad;            /* [T_local][4] fp64: pairs, Rss00, Rss11, Rss01, or NULL */
     double* work;            /* >= ame_mstep_work_size() doubles */
+    const uint64_t* Mt;      /* [T_local][n][nw] packed mask (ame_pack_mask), or NULL */
+    int32_t mask_select;     /* 0, AME_MASK_OBSERVED or AME_MASK_HIDDEN: the pairs the dyad
+                                statistics run over (dyad[0] counts them); needs Mt */
 } ame_mstep_args;
 int ame_mstep_stats(const ame_dims* dims, const ame_mstep_args* args, void* stream);
 /* Scratch doubles ame_mstep_stats needs (chunk partials, feature rows, tile
@@ -498,6 +511,58 @@ long long ame_covar_work_size(const ame_dims* dims, int p);
  * any plane of Wt (checked). */
 int ame_covar_resid(const ame_dims* dims, const float* Yt_raw, const float* Wt, const double* beta,
                     int p, float* Yt_out, void* stream);
+
+/* ---- missing dyads ---------------------------------------------------------------
+ * Replaces nothing the reference computes: it assumes every dyad observed.  The
+ * unit is the unordered pair {i, j} of one slice.  ame_sweep, ame_cov and
+ * ame_elbo take no mask: they run on a working network in which the two
+ * entries of a hidden pair hold each node's own-perspective mean,
+ *   Yt[t][i][j] = (a_i + u_i.v_j, b_i + v_i.u_j),
+ *   Yt[t][j][i] = (a_j + u_j.v_i, b_j + v_j.u_i),
+ * the value J_j m_i at which y_ij drops out of node i's update
+ * (structured_mf.py:289-326 treats y_ij as J_j x_i + noise).  Refilled from the
+ * new means after every sweep, the damped iteration converges to the fixed
+ * point of the reference's rule restricted to observed partners (up to its 1e-6
+ * jitter).  The covariances stay those of the fully observed precision.
+ *
+ * Mask layout: Mt[T_local][n][nw] uint64, nw = ceil(n / 64); bit j & 63 of word
+ * j >> 6 in row i is 1 when {i, j} is hidden at that slice; bits at j >= n and
+ * at j == i are 0.
+ * ame_pack_mask: M is uint8 [n][n][T_total] (non-zero = hidden; the diagonal is
+ * ignored); the slices [t_begin, t_begin + T_local) are packed.  pairs[T_local]
+ * (uint64) = hidden pairs i < j per slice, deg[T_local][n] (uint32) = observed
+ * partners of each node, *asym (uint64) = ordered entries i != j of the packed
+ * slices with M[i][j] != M[j][i] as booleans (two per disagreeing pair).  The
+ * call zeroes pairs and asym itself (on the stream).  Integer counts only: the
+ * same bits on every run.
+ * ame_fill_missing: one workgroup per (slice, 64 x 64 tile of the upper
+ * triangle).  A tile with no hidden pair returns after reading its 64 mask
+ * words.  Otherwise p = u_i.v_j and q = u_j.v_i of the tile run on fp32 MFMA and
+ * every hidden pair i < j gets Yt[t][i][j] = (a_i + p, b_i + q) and Yt[t][j][i]
+ * = (a_j + q, b_j + p), fp32 adds; no other element of Yt is written.  Per slice
+ *   corr[t][0] = sum_{hidden i<j} r_up' R_inv r_up
+ *   corr[t][1] = sum_{hidden i<j} (|r_up|^2 + |r_lo|^2)
+ * in fp64, r_up = Yt[t][i][j] - (a_i + b_j + p, a_j + b_i + q) and r_lo =
+ * Yt[t][j][i] - (a_j + b_i + q, a_i + b_j + p) of the values just stored: what
+ * ame_elbo's out[0] and out[7] accumulate at the hidden entries.  Tile partials
+ * are added by a second kernel in tile order: no atomics, no waits, the same
+ * bits from run to run and for any split of the slices over calls (dims.t_begin
+ * / T_total / variant are only range-checked). */
+typedef struct ame_fill_args {
+    const float* x;      /* [T_local][n][d] means                                        */
+    const uint64_t* Mt;  /* [T_local][n][nw] packed mask                                 */
+    float* Yt;           /* [T_local][n][ny][2] working network, hidden entries written  */
+    double rinv[4];      /* R_inv row-major                                              */
+    double* corr;        /* [T_local][2] fp64                                            */
+    double* work;        /* >= ame_fill_work_size() doubles                              */
+} ame_fill_args;
+/* Words of Mt for these dims (T_local * n * ceil(n / 64)), -1 on bad dims. */
+long long ame_mask_words(const ame_dims* dims);
+int ame_pack_mask(const uint8_t* M, uint64_t* Mt, const ame_dims* dims, uint64_t* pairs, uint32_t* deg,
+                  uint64_t* asym, void* stream);
+int ame_fill_missing(const ame_dims* dims, const ame_fill_args* args, void* stream);
+/* Scratch doubles ame_fill_missing needs (2 per tile), -1 on bad dims. */
+long long ame_fill_work_size(const ame_dims* dims);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

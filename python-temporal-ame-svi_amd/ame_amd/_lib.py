@@ -74,12 +74,13 @@ class ame_predict_args(ctypes.Structure):
     _fields_ = [("x", c_vp), ("cov", c_vp), ("Yt", c_vp), ("noise", ctypes.c_double * 4),
                 ("n_levels", c_int32), ("zsq", ctypes.c_double * AME_PREDICT_MAX_LEVELS),
                 ("csq", ctypes.c_double * AME_PREDICT_MAX_LEVELS), ("sums", c_vp), ("dense", c_vp),
-                ("i0", c_int32), ("i1", c_int32), ("j0", c_int32), ("j1", c_int32), ("work", c_vp)]
+                ("i0", c_int32), ("i1", c_int32), ("j0", c_int32), ("j1", c_int32), ("work", c_vp),
+                ("Mt", c_vp), ("mask_select", c_int32)]
 
 
 class ame_mstep_args(ctypes.Structure):
     _fields_ = [("x", c_vp), ("cov", c_vp), ("prev_final", c_vp), ("Yt", c_vp), ("state", c_vp),
-                ("dyad", c_vp), ("work", c_vp)]
+                ("dyad", c_vp), ("work", c_vp), ("Mt", c_vp), ("mask_select", c_int32)]
 
 
 AME_SMOOTH_STAGE_OBS, AME_SMOOTH_STAGE_SOLVE = 1, 2
@@ -101,9 +102,18 @@ class ame_covar_args(ctypes.Structure):
                 ("work", c_vp), ("work_doubles", ctypes.c_uint64)]
 
 
+# missing dyads: mask_select of ame_predict_args / ame_mstep_args
+AME_MASK_OBSERVED, AME_MASK_HIDDEN = 1, 2
+
+
+class ame_fill_args(ctypes.Structure):
+    _fields_ = [("x", c_vp), ("Mt", c_vp), ("Yt", c_vp), ("rinv", ctypes.c_double * 4), ("corr", c_vp),
+                ("work", c_vp)]
+
+
 # every symbol include/ame_amd.h declares (checked by tests/test_capi.py)
 EXPORTS = ("ame_pack_y", "ame_pack_y_size", "ame_sweep", "ame_sweep_kind", "ame_sweep_work_size", "ame_sweep_orders_slices", "ame_sweep_max_slices", "ame_sweep_slice_workgroups", "ame_sweep_lds_bytes", "ame_cov",
-           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_smooth", "ame_smooth_work_size", "ame_smooth_lds_bytes", "ame_covar_stats", "ame_covar_work_size", "ame_covar_resid", "ame_host_register", "ame_host_unregister",
+           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_smooth", "ame_smooth_work_size", "ame_smooth_lds_bytes", "ame_covar_stats", "ame_covar_work_size", "ame_covar_resid", "ame_mask_words", "ame_pack_mask", "ame_fill_missing", "ame_fill_work_size", "ame_host_register", "ame_host_unregister",
            "ame_stream_create_cu_range", "ame_stream_destroy",
            "ame_peer_alloc", "ame_peer_free", "ame_peer_open", "ame_peer_close",
            "ame_peer_probe", "ame_peer_read_u64", "ame_peer_clear",
@@ -151,6 +161,14 @@ def _declare(L):
     L.ame_covar_work_size.restype = ctypes.c_longlong
     L.ame_covar_resid.argtypes = [P(ame_dims), c_vp, c_vp, P(ctypes.c_double), ctypes.c_int, c_vp, c_vp]
     L.ame_covar_resid.restype = ctypes.c_int
+    L.ame_mask_words.argtypes = [P(ame_dims)]
+    L.ame_mask_words.restype = ctypes.c_longlong
+    L.ame_pack_mask.argtypes = [c_vp, c_vp, P(ame_dims), c_vp, c_vp, c_vp, c_vp]
+    L.ame_pack_mask.restype = ctypes.c_int
+    L.ame_fill_missing.argtypes = [P(ame_dims), P(ame_fill_args), c_vp]
+    L.ame_fill_missing.restype = ctypes.c_int
+    L.ame_fill_work_size.argtypes = [P(ame_dims)]
+    L.ame_fill_work_size.restype = ctypes.c_longlong
     L.ame_debug_selftest.argtypes = [c_vp, c_vp]
     L.ame_debug_selftest.restype = ctypes.c_int
     if hasattr(L, "ame_debug_occupy"):   # diagnostic; absent from older A/B builds

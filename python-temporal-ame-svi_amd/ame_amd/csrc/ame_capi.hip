@@ -41,6 +41,12 @@ long long ame_covar_work_doubles(const ame_dims*, int p);
 long long ame_covar_blocks(const ame_dims*);
 long long ame_covar_plane4(const ame_dims*);
 int ame_pack_dispatch(const float*, float*, const ame_dims*, unsigned long long*, hipStream_t);
+int ame_pack_mask_dispatch(const uint8_t* M, unsigned long long* Mt, const ame_dims*, unsigned long long* pairs,
+                           uint32_t* deg, unsigned long long* asym, hipStream_t);
+int ame_fill_missing_dispatch(const ame_dims*, const ame_fill_args*, hipStream_t);
+long long ame_mask_words_count(const ame_dims*);
+long long ame_fill_work_doubles(const ame_dims*);
+long long ame_fill_blocks(const ame_dims*);
 
 static thread_local char g_err[512] = "";
 
@@ -431,6 +437,57 @@ int ame_elbo_pairs_diag(const ame_dims* dims, const ame_elbo_args* a, void* stre
     return launched(ame_elbo_dispatch(dims, a, (hipStream_t)stream, 1), "elbo_pairs");
 }
 
+// mask_select of ame_predict_args / ame_mstep_args: a known value, and a mask when it selects
+static int check_mask_select(const char* who, int sel, const void* Mt) {
+    if (sel != 0 && sel != AME_MASK_OBSERVED && sel != AME_MASK_HIDDEN) {
+        snprintf(g_err, sizeof(g_err), "%s: unknown mask_select %d", who, sel);
+        return -1;
+    }
+    if (sel != 0 && !Mt) {
+        snprintf(g_err, sizeof(g_err), "%s: mask_select=%d needs the packed mask Mt (NULL)", who, sel);
+        return -1;
+    }
+    return 0;
+}
+
+long long ame_mask_words(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_mask_words_count(dims);
+}
+
+int ame_pack_mask(const uint8_t* M, uint64_t* Mt, const ame_dims* dims, uint64_t* pairs, uint32_t* deg,
+                  uint64_t* asym, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!M || !Mt || !pairs || !deg || !asym)
+        return fail("ame_pack_mask: NULL buffer (M, Mt, pairs, deg, asym)");
+    if (((uintptr_t)Mt | (uintptr_t)pairs | (uintptr_t)asym) & 7)
+        return fail("ame_pack_mask: Mt, pairs and asym must be 8-byte aligned");
+    if ((uintptr_t)deg & 3) return fail("ame_pack_mask: deg must be 4-byte aligned");
+    if ((long long)dims->T_local * dims->n > 0x7FFFFFFFLL)
+        return fail("ame_pack_mask: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_pack_mask_dispatch(M, (unsigned long long*)Mt, dims, (unsigned long long*)pairs, deg,
+                                           (unsigned long long*)asym, (hipStream_t)stream), "pack_mask");
+}
+
+long long ame_fill_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_fill_work_doubles(dims);
+}
+
+int ame_fill_missing(const ame_dims* dims, const ame_fill_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_fill_missing: args is NULL");
+    if (!a->x || !a->Mt || !a->Yt || !a->corr || !a->work)
+        return fail("ame_fill_missing: NULL buffer (x, Mt, Yt, corr, work)");
+    if (((uintptr_t)a->Mt | (uintptr_t)a->Yt | (uintptr_t)a->corr | (uintptr_t)a->work) & 7)
+        return fail("ame_fill_missing: Mt, Yt, corr and work must be 8-byte aligned");
+    if (ame_fill_blocks(dims) > 0x7FFFFFFFLL)
+        return fail("ame_fill_missing: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_fill_missing_dispatch(dims, a, (hipStream_t)stream), "fill_missing");
+}
+
 long long ame_predict_work_size(const ame_dims* dims) {
     if (check_dims(dims)) return -1;
     return ame_predict_work_doubles(dims);
@@ -442,6 +499,8 @@ int ame_predict(const ame_dims* dims, const ame_predict_args* a, void* stream) {
     if (a->n_levels < 0 || a->n_levels > AME_PREDICT_MAX_LEVELS)
         return fail("ame_predict: n_levels=%d outside [0, %d]", a->n_levels, AME_PREDICT_MAX_LEVELS);
     if (a->sums && !a->Yt) return fail("ame_predict: sums need the observations Yt (NULL)");
+    if (int e = check_mask_select("ame_predict", a->mask_select, a->Mt)) return e;
+    if (a->mask_select != 0 && !a->sums) return fail("ame_predict: mask_select=%d without sums", a->mask_select);
     if (a->dense) {
         if (a->i0 < 0 || a->i0 >= a->i1 || a->i1 > dims->n)
             return fail("ame_predict: dense rows [%d, %d) outside [0, n]", a->i0, a->i1);
@@ -464,6 +523,8 @@ int ame_mstep_stats(const ame_dims* dims, const ame_mstep_args* a, void* stream)
     if (!a || !a->x || !a->cov || !a->work) return fail("ame_mstep_stats: NULL buffer (x, cov, work)");
     if (!a->state && !a->dyad) return fail("ame_mstep_stats: state and dyad are both NULL");
     if (a->dyad && !a->Yt) return fail("ame_mstep_stats: dyad statistics need the observations Yt (NULL)");
+    if (int e = check_mask_select("ame_mstep_stats", a->mask_select, a->Mt)) return e;
+    if (a->mask_select != 0 && !a->dyad) return fail("ame_mstep_stats: mask_select=%d without dyad", a->mask_select);
     if (a->state && dims->t_begin > 0 && !a->prev_final)
         return fail("ame_mstep_stats: t_begin=%d > 0 needs prev_final", dims->t_begin);
     if ((a->state && ame_mstep_state_blocks(dims) > 0x7FFFFFFFLL) ||

@@ -68,7 +68,17 @@ struct PredictParams {
     double zsq[AME_PREDICT_MAX_LEVELS], csq[AME_PREDICT_MAX_LEVELS];
     double* partial;   // [S][ntile][AME_PNS]
     float* dense;
+    const unsigned long long* Mt;   // [S][n][nw] packed mask, or nullptr
+    int nw, mask_select;            // 0: every pair i < j; AME_MASK_OBSERVED / AME_MASK_HIDDEN
 };
+
+// whether pair (i, j), i < j < n, of slice tl is selected (MODE 0 scoring, MODE 2 statistics)
+__device__ __forceinline__ bool predict_pair_selected(const PredictParams& p, int tl, int i, int j) {
+    if (p.mask_select == 0) return true;
+    const unsigned long long wd = p.Mt[((size_t)tl * p.n + i) * p.nw + (j >> 6)];
+    const bool hidden = (wd >> (j & 63)) & 1ull;
+    return hidden == (p.mask_select == AME_MASK_HIDDEN);
+}
 
 // ---------------------------------------------------------------------------
 // K1: feature rows
@@ -276,7 +286,7 @@ ame_predict_pairs_kernel(PredictParams p) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int i = I0 + 16 * w + 4 * lq + g;
-                if (i < n && j < n && i < j) {
+                if (i < n && j < n && i < j && predict_pair_selected(p, tl, i, j)) {
                     const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
                     const double e0 = (double)y.x - (double)acc[0][s][g];
                     const double e1 = (double)y.y - (double)acc[1][s][g];
@@ -307,7 +317,7 @@ ame_predict_pairs_kernel(PredictParams p) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int i = I0 + 16 * w + 4 * lq + g;
-                if (i < n && j < n && i < j) {
+                if (i < n && j < n && i < j && predict_pair_selected(p, tl, i, j)) {
                     const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
                     const double e0 = (double)y.x - (double)acc[0][s][g];
                     const double e1 = (double)y.y - (double)acc[1][s][g];
@@ -467,6 +477,9 @@ static int launch_predict(const ame_dims* dm, const ame_predict_args* a, hipStre
     }
     p.partial = a->work + predict_feat_doubles(dm);
     p.dense = nullptr;
+    p.Mt = (const unsigned long long*)a->Mt;
+    p.nw = (n + 63) / 64;
+    p.mask_select = a->mask_select;
     if (a->sums) {
         p.ntile = (int)predict_tri_tiles(n);
         hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 0>), dim3((unsigned)((long long)S * p.ntile)),
@@ -507,6 +520,9 @@ static int launch_mstep_dyad(const ame_dims* dm, const ame_mstep_args* a, double
     for (int l = 0; l < AME_PREDICT_MAX_LEVELS; ++l) p.zsq[l] = p.csq[l] = 0.0;
     p.partial = work + predict_feat_doubles(dm);
     p.dense = nullptr;
+    p.Mt = (const unsigned long long*)a->Mt;
+    p.nw = (n + 63) / 64;
+    p.mask_select = a->mask_select;
     p.ntile = (int)predict_tri_tiles(n);
     hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 2>), dim3((unsigned)((long long)S * p.ntile)),
                        dim3(AME_NT), 0, st, p);

@@ -32,6 +32,12 @@ of its slices waits on the device for the previous sweep to finish slices t
 and t+1, so consecutive sweeps overlap and the wavefront fill is paid once per
 fit() instead of once per iteration.  Results are bit-identical to running
 the kernels in order (tests/test_gpu_parity.py::test_speculative_sweep_is_exact).
+
+With hidden dyads (model.set_missing) the engine also owns Yt_raw (the packed
+observations; Yt is then a separate working network), Mt / pairs / deg (the
+packed mask, ame_pack_mask) and corr, and runs ame_fill_missing on the main
+stream after every committed sweep, before that state's ELBO; sweeps then run
+in order, none started ahead.
 """
 from __future__ import annotations
 
@@ -39,7 +45,7 @@ import collections
 import ctypes
 import math
 import time
-from dataclasses import dataclass, fields
+from dataclasses import dataclass, fields, replace
 from typing import Optional
 
 import torch
@@ -215,20 +221,34 @@ class Constants:
         return (ctypes.c_double * 4)(*r)
 
 
-def assemble(out, n, T, d, variant, C: Constants):
+def assemble(out, n, T, d, variant, C: Constants, hidden=None, pairs_obs=None, deg_trace=None):
     """ELBO pieces and MSE from the 8 device sums (see include/ame_amd.h).
 
     Formulas: structured_mf.py:124-209 / naive_mf.py:114-191 and
     temporal_ame.py:290 with the pairwise correction collapsed as
     sum_{i<j}(tr_i + tr_j) = (n-1) sum_i tr_i.
+
+    With hidden dyads (all three optional arguments): ``hidden`` = the two
+    correction sums of ame_fill_missing added over the slices, which out[0] and
+    out[7] accumulated at the hidden entries of the working network and are
+    taken off again; ``pairs_obs`` = observed pairs; ``deg_trace`` = sum_{i,t}
+    deg[t][i] tr(S_it), each node's trace counted once per observed partner
+    ((n - 1) out[1] when nothing is hidden).  The formulas are then the
+    reference's over observed pairs.
     """
-    npairs = T * n * (n - 1) / 2.0
-    corr = 0.0 if variant == "naive" else 0.1 * C.trRinv / d * (n - 1) * out[1]
-    loglik = -0.5 * (npairs * (C.logdetR + 2 * LOG2PI) + out[0] + corr)
+    if pairs_obs is None:
+        npairs = T * n * (n - 1) / 2.0
+        corr = 0.0 if variant == "naive" else 0.1 * C.trRinv / d * (n - 1) * out[1]
+        quad, sq = out[0], out[7]
+    else:
+        npairs = float(pairs_obs)
+        corr = 0.0 if variant == "naive" else 0.1 * C.trRinv / d * deg_trace
+        quad, sq = out[0] - hidden[0], out[7] - hidden[1]
+    loglik = -0.5 * (npairs * (C.logdetR + 2 * LOG2PI) + quad + corr)
     prior0 = -0.5 * (n * (C.logdetS0 + d * LOG2PI) + out[2] + out[3])
     trans = -0.5 * (n * (T - 1) * (C.logdetQ + d * LOG2PI) + out[4] + out[5])
     ent = 0.5 * (n * T * d * (1 + LOG2PI) + out[6])
-    recon = out[7] / (n * (n - 1) * T)
+    recon = sq / (n * (n - 1) * T) if pairs_obs is None else sq / (2.0 * npairs)
     return {"loglik": loglik, "prior0": prior0, "trans": trans, "entropy": ent,
             "elbo": loglik + prior0 + trans + ent, "recon": recon}
 
@@ -304,6 +324,17 @@ class DeviceEngine:
                 halo is not None or self.shard.T_local != self.shard.T_total):
             raise NotImplementedError("dyadic covariates are not available on a time-sharded run")
         self.options = opt = EngineOptions.coerce(options)
+        # hidden dyads (model.set_missing): the working network is refilled from
+        # the new means after every sweep, so sweeps run in order, none started
+        # ahead
+        self.masked = getattr(model, "missing", None) is not None
+        if self.masked:
+            if halo is not None or self.shard.T_local != self.shard.T_total:
+                raise NotImplementedError("missing dyads are not available on a time-sharded run")
+            if getattr(model, "W", None) is not None:
+                raise NotImplementedError("missing dyads together with dyadic covariates are not "
+                                          "available (ame_covar_stats does not select pairs)")
+            self.options = opt = replace(opt, pipeline=False, speculate=False)
         self.lr = float(lr)
         self.C = Constants(model)
         sh = self.shard
@@ -346,6 +377,8 @@ class DeviceEngine:
         self._out_host = None
         self._out_valid = False
         self._cov_terms_valid = False
+        self._fill_valid = False
+        self._hidden_host = None
         self.timing = False       # record HIP events around each kernel launch
         self.events = []          # (name, start, end) while timing
         self.speculation = bool(opt.speculate)
@@ -390,7 +423,88 @@ class DeviceEngine:
         self._covar_H = None
         if getattr(model, "W", None) is not None:
             self._init_covariates(model)
+        if self.masked:
+            self._init_missing(model.missing)
         self._mark_host_writes()
+
+    # ------------------------------------------------------------------
+    # missing dyads (ame_pack_mask / ame_fill_missing)
+    # ------------------------------------------------------------------
+    def pack_mask(self, mask, what="mask"):
+        """(n, n, S) bool / uint8 mask -> (Mt [S][n][nw] int64, pairs [S] int64,
+        deg [S][n] int32) on the device (ame_pack_mask); an asymmetric mask
+        raises ValueError."""
+        m = torch.as_tensor(mask)
+        if m.dim() != 3 or tuple(m.shape[:2]) != (self.n, self.n) or m.shape[2] < 1:
+            raise ValueError(f"{what} has shape {tuple(m.shape)}, expected ({self.n}, {self.n}, S)")
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"{what} has dtype {m.dtype}, expected bool or uint8")
+        S = int(m.shape[2])
+        nw = (self.n + 63) // 64
+        dims = _lib.ame_dims(self.n, self.r, S, 0, S, self.vcode)
+        with torch.cuda.device(self.dev):
+            src = m.detach().to(torch.uint8).to(self.dev).contiguous()
+            Mt = torch.empty(S, self.n, nw, dtype=torch.int64, device=self.dev)
+            pairs = torch.empty(S, dtype=torch.int64, device=self.dev)
+            deg = torch.empty(S, self.n, dtype=torch.int32, device=self.dev)
+            asym = torch.empty(1, dtype=torch.int64, device=self.dev)
+        _lib.check(self.L.ame_pack_mask(_ptr(src), _ptr(Mt), ctypes.byref(dims), _ptr(pairs), _ptr(deg),
+                                        _ptr(asym), self._sp()), "ame_pack_mask")
+        bad = int(asym.item())
+        del src
+        if bad:
+            raise ValueError(f"{what} is not symmetric: {bad // 2} pair(s) with mask[i, j, t] != "
+                             "mask[j, i, t] (the unit is the unordered pair)")
+        return Mt, pairs, deg
+
+    def _init_missing(self, mask):
+        """Pack the mask once, keep the packed observations as Yt_raw and make Yt
+        a separate working buffer (a copy: observed entries are never written
+        again, hidden ones are overwritten by every fill)."""
+        if tuple(mask.shape) != (self.n, self.n, self.T):
+            raise ValueError(f"mask has shape {tuple(mask.shape)}, expected ({self.n}, {self.n}, {self.T})")
+        self.Mt, self.pairs, self.deg = self.pack_mask(mask)
+        self.hidden_pairs = [int(v) for v in self.pairs.cpu().tolist()]
+        self.pairs_obs = self.T * self.n * (self.n - 1) // 2 - sum(self.hidden_pairs)
+        if self.pairs_obs < 1:
+            raise ValueError("every dyad is hidden: nothing to fit")
+        with torch.cuda.device(self.dev):
+            self.Yt_raw = self.Yt
+            self.Yt = self.Yt_raw.clone()
+            self.corr = torch.zeros(self.T, 2, dtype=torch.float64, device=self.dev)
+            ws = int(self.L.ame_fill_work_size(ctypes.byref(self.dims)))
+            if ws < 0:
+                _lib.check(-1, "ame_fill_work_size")
+            self.fill_work = torch.empty(ws, dtype=torch.float64, device=self.dev)
+            self._deg64 = self.deg.double()
+        if sum(self.hidden_pairs):   # the two rows of a hidden pair hold different values
+            self.swap_consistent = False
+        self._fill_valid = False
+        self._hidden_host = None
+
+    def fill_missing(self):
+        """Refill the hidden entries of the working network from the current
+        means, on the main stream (ame_fill_missing): after the sweep that
+        produced them has been committed there, before the ELBO of that state and
+        before the next sweep, which is ordered after the main stream."""
+        a = _lib.ame_fill_args(x=_ptr(self.x_a), Mt=_ptr(self.Mt), Yt=_ptr(self.Yt), rinv=self.C.rinv4(),
+                               corr=_ptr(self.corr), work=_ptr(self.fill_work))
+        tok = self._tic("fill")
+        _lib.check(self.L.ame_fill_missing(ctypes.byref(self.dims), ctypes.byref(a), self._sp()),
+                   "ame_fill_missing")
+        self._toc(tok)
+        self._fill_valid = True
+        self._hidden_host = None
+
+    def mask_args(self, select):
+        """(Yt, Mt, mask_select) for predict / mstep_stats: the packed observations
+        (never the working network) with the mask and a selector, or the
+        network every kernel reads when nothing is masked."""
+        if not self.masked:
+            if select:
+                raise ValueError("a subset needs a mask (model.set_missing)")
+            return self.Yt, None, 0
+        return self.Yt_raw, self.Mt, int(select)
 
     # ------------------------------------------------------------------
     # dyadic covariates (ame_covar_stats / ame_covar_resid)
@@ -697,6 +811,7 @@ class DeviceEngine:
         self._cur = slot
         self._out_valid = False
         self._cov_terms_valid = False
+        self._fill_valid = False
 
     def sweep(self):
         """One Gauss-Seidel sweep + covariance update (reference _update_step).
@@ -704,10 +819,14 @@ class DeviceEngine:
         if self._specs:
             done, slot = self._specs.popleft()
         else:
+            if self.masked and not self._fill_valid:   # first sweep, or after set_means
+                self.fill_missing()
             done, slot = self._launch_sweep()
         for ev in done:
             self.stream.wait_event(ev)
         self._commit(slot)
+        if self.masked:   # one fill serves this state's ELBO correction and the next sweep
+            self.fill_missing()
         if self.halo is not None:
             self.halo.after_sweep(self)
 
@@ -744,6 +863,8 @@ class DeviceEngine:
         which writes no sums."""
         if not pairs_only and not self._cov_terms_valid:
             self.refresh_cov_terms()
+        if self.masked and not self._fill_valid:
+            self.fill_missing()
         prev_final = None
         if self.halo is not None and not pairs_only:
             prev_final = self.halo.prev_final(self)
@@ -780,7 +901,22 @@ class DeviceEngine:
         return self._out_host
 
     def terms(self, speculate=0):
-        return assemble(self.sums(speculate), self.n, self.T, self.d, self.variant, self.C)
+        out = self.sums(speculate)
+        if not self.masked:
+            return assemble(out, self.n, self.T, self.d, self.variant, self.C)
+        if self._hidden_host is None:
+            # the state's correction sums, slice by slice in time order, and each
+            # node's trace once per observed partner, from cov_terms on the device
+            rows = self.corr.cpu().tolist()
+            hid = [0.0, 0.0]
+            for row in rows:
+                hid[0] += row[0]
+                hid[1] += row[1]
+            tr = self.cov_terms.view(self.T, self.n, 4)[:, :, 1]
+            self._hidden_host = (hid, float((self._deg64 * tr).sum().item()))
+        hid, deg_trace = self._hidden_host
+        return assemble(out, self.n, self.T, self.d, self.variant, self.C, hidden=hid,
+                        pairs_obs=self.pairs_obs, deg_trace=deg_trace)
 
     def _check_status(self):
         words = self.status.cpu().tolist()
@@ -795,6 +931,8 @@ class DeviceEngine:
     def invalidate(self):
         self._out_valid = False
         self._cov_terms_valid = False
+        self._fill_valid = False
+        self._hidden_host = None
 
     # ------------------------------------------------------------------
     # state transfer (reference layout (n, T, d[, d]))
@@ -849,12 +987,15 @@ class DeviceEngine:
                    "ame_pack_y")
         return Yt
 
-    def predict(self, x, cov, Yt=None, include_noise=True, zsq=(), csq=(), block=None):
+    def predict(self, x, cov, Yt=None, include_noise=True, zsq=(), csq=(), block=None, Mt=None,
+                mask_select=0):
         """ame_predict over a stack of slices: x [S][n][d], cov [S][n][d][d]
         (device, fp32, contiguous).  Yt [S][n][ny][2] -> per-slice sums
         [S][AME_PREDICT_SUMS] (fp64, device); block = (i0, i1, j0, j1) -> dense
         [S][i1-i0][j1-j0][5] (fp32, device).  Returns (sums or None, dense or
-        None).  Runs on the ELBO stream; the caller has dropped speculation."""
+        None).  Mt [S][n][nw] (ame_pack_mask) with mask_select = _lib.AME_MASK_OBSERVED
+        / AME_MASK_HIDDEN scores only those pairs.  Runs on the ELBO stream; the
+        caller has dropped speculation."""
         S = int(x.shape[0])
         n, d = self.n, self.d
         assert tuple(x.shape) == (S, n, d) and tuple(cov.shape) == (S, n, d, d)
@@ -880,7 +1021,8 @@ class DeviceEngine:
                     csq=(ctypes.c_double * _lib.AME_PREDICT_MAX_LEVELS)(*csq),
                     sums=_ptr(sums[s0:s1]) if sums is not None else None,
                     dense=_ptr(dense[s0:s1]) if dense is not None else None,
-                    work=_ptr(wk))
+                    work=_ptr(wk), Mt=_ptr(Mt[s0:s1]) if Mt is not None else None,
+                    mask_select=int(mask_select))
                 if block is not None:
                     a.i0, a.i1, a.j0, a.j1 = i0, i1, j0, j1
                 _lib.check(self.L.ame_predict(ctypes.byref(dm), ctypes.byref(a), sp), "ame_predict")
@@ -903,6 +1045,8 @@ class DeviceEngine:
         chunk, wk = self._slice_chunk(self.L.ame_mstep_work_size, TL)
         if x is None:
             x, cov = self.x_a, self.cov
+        # with hidden dyads: the packed observations and the observed pairs only
+        Yt, Mt, sel = self.mask_args(_lib.AME_MASK_OBSERVED if self.masked else 0)
         with torch.cuda.device(self.dev):
             state = torch.empty(TL, 2, d, d, dtype=torch.float64, device=self.dev)
             dyad = torch.empty(TL, 4, dtype=torch.float64, device=self.dev)
@@ -913,8 +1057,8 @@ class DeviceEngine:
                 a = _lib.ame_mstep_args(
                     x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]),
                     prev_final=prev_final if s0 == 0 else _ptr(x[s0 - 1]),
-                    Yt=_ptr(self.Yt[s0:s1]), state=_ptr(state[s0:s1]), dyad=_ptr(dyad[s0:s1]),
-                    work=_ptr(wk))
+                    Yt=_ptr(Yt[s0:s1]), state=_ptr(state[s0:s1]), dyad=_ptr(dyad[s0:s1]),
+                    work=_ptr(wk), Mt=_ptr(Mt[s0:s1]) if Mt is not None else None, mask_select=sel)
                 _lib.check(self.L.ame_mstep_stats(ctypes.byref(dm), ctypes.byref(a), sp),
                            "ame_mstep_stats")
         return state, dyad
@@ -945,6 +1089,9 @@ class DeviceEngine:
         RuntimeError (its outputs are NaN).  Runs on the ELBO stream."""
         if self.halo is not None or self.shard.T_local != self.shard.T_total:
             raise NotImplementedError("smooth is not available on a time-sharded run")
+        if self.masked:
+            raise NotImplementedError("smooth is not available with missing dyads: its observation "
+                                      "stage has no mask")
         self.discard_speculation()
         n, d, T = self.n, self.d, self.shard.T_local
         chunk = self.smooth_chunk()

@@ -310,6 +310,9 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         if self._time_sharded():
             raise NotImplementedError("smooth is not available on a time-sharded run: the forward "
                                       "pass would have to carry (J_t^-1, g_t) across ranks")
+        if getattr(self.model, "missing", None) is not None:
+            raise NotImplementedError("smooth() / smoothed=True are not available with missing dyads: "
+                                      "the observation stage of ame_smooth has no mask")
         eng = self._predict_engine()
         return SmoothResult(*eng.smooth())
 
@@ -322,7 +325,23 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         eng = self._predict_engine()
         return eng, eng.x_a, eng.cov, None
 
-    def predictive_check(self, levels=(0.5, 0.9, 0.95), include_noise=True, smoothed=False) -> dict:
+    _SUBSETS = {"observed": 1, "held_out": 2}   # AME_MASK_OBSERVED / AME_MASK_HIDDEN
+
+    def _subset(self, subset):
+        """mask_select of a predictive_check subset: "observed" by default with a
+        mask (model.set_missing); any subset without one is a ValueError."""
+        if getattr(self.model, "missing", None) is None:
+            if subset is not None:
+                raise ValueError(f"subset={subset!r} needs a mask (model.set_missing)")
+            return 0
+        if subset is None:
+            subset = "observed"
+        if subset not in self._SUBSETS:
+            raise ValueError(f"subset must be one of {sorted(self._SUBSETS)} (got {subset!r})")
+        return self._SUBSETS[subset]
+
+    def predictive_check(self, levels=(0.5, 0.9, 0.95), include_noise=True, smoothed=False,
+                         subset=None) -> dict:
         """Score the observed network against the posterior-predictive moments of
         every dyad, in-sample.  fp64 arrays of length T: ``pairs``, ``log_score``
         (sum of log N(y_ij; E mu_ij, Sigma_ij) over pairs i < j), ``mahalanobis``,
@@ -331,11 +350,16 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         include_noise=False scores against the credible region of the mean.
         smoothed=True scores the smoothed means and covariances (:meth:`smooth`)
         instead of the fit's.  Time-sharded: a collective, every rank returns all
-        T steps."""
+        T steps.  With hidden dyads (model.set_missing) ``subset`` chooses the
+        pairs: "observed" (the default) scores the pairs the fit has seen,
+        "held_out" the hidden ones against ``model.Y``, out of sample; ``pairs``
+        counts the chosen ones."""
         levels, zsq, csq = self._thresholds(levels)
+        select = self._subset(subset)
         eng, x, cov, _ = self._state(smoothed)
-        sums, _ = eng.predict(x, cov, Yt=eng.Yt, include_noise=include_noise,
-                              zsq=zsq, csq=csq)
+        Yt, Mt, select = eng.mask_args(select)
+        sums, _ = eng.predict(x, cov, Yt=Yt, include_noise=include_noise,
+                              zsq=zsq, csq=csq, Mt=Mt, mask_select=select)
         if self._halo is not None:
             sums = self._halo.gather_time(sums.unsqueeze(0), 1)[0]
         return self._check_dict(sums, levels)
@@ -414,11 +438,13 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         return m.permute(1, 0, 2).to("cpu").contiguous(), S.permute(1, 0, 2, 3).to("cpu").contiguous()
 
     def forecast_check(self, Y_future, levels=(0.5, 0.9, 0.95), include_noise=True,
-                       smoothed=False, W_future=None) -> dict:
+                       smoothed=False, W_future=None, missing_future=None) -> dict:
         """predictive_check of held-out steps: ``Y_future`` (n, n, h, 2) scored
         against the h-step forecast; the same dictionary, of length h.  A model
         with covariates needs theirs for those steps, ``W_future`` (p, n, n, h,
-        2): the residual Y_future - sum_k beta_k W_future[k] is scored."""
+        2): the residual Y_future - sum_k beta_k W_future[k] is scored.
+        ``missing_future`` (n, n, h), bool or uint8 and symmetric as in
+        model.set_missing: only the observed future pairs are scored."""
         levels, zsq, csq = self._thresholds(levels)
         Y_future = torch.as_tensor(Y_future)
         Wf = self._future_covariates(W_future, Y_future.shape[2] if Y_future.dim() == 4 else 1)
@@ -427,7 +453,16 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         eng, (m, S) = self._forecast_states(int(Y_future.shape[2]) if Y_future.dim() == 4 else 1,
                                             smoothed)
         Yt = eng.pack_future(Y_future)
-        sums, _ = eng.predict(m, S, Yt=Yt, include_noise=include_noise, zsq=zsq, csq=csq)
+        Mt, select = None, 0
+        if missing_future is not None:
+            mf = torch.as_tensor(missing_future)
+            if mf.dim() != 3 or int(mf.shape[2]) != int(Yt.shape[0]):
+                raise ValueError(f"missing_future has shape {tuple(mf.shape)}, expected "
+                                 f"({self.n}, {self.n}, {int(Yt.shape[0])})")
+            Mt, _, _ = eng.pack_mask(mf, "missing_future")
+            select = self._SUBSETS["observed"]
+        sums, _ = eng.predict(m, S, Yt=Yt, include_noise=include_noise, zsq=zsq, csq=csq, Mt=Mt,
+                              mask_select=select)
         return self._check_dict(sums, levels)
 
     def forecast_dyads(self, n_steps: int = 1, rows=None, cols=None, include_noise=True,
@@ -454,6 +489,9 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         """fp64 CPU tensors ``A0, A11, A00, A10`` (d, d), ``Rss`` (2, 2) and the
         pair count ``pairs`` of the current q.  Time-sharded: a collective; every
         rank adds all T slices in time order and returns the same bits.
+        With hidden dyads (model.set_missing) ``Rss`` and ``pairs`` run over the
+        observed pairs only, so the M-step's R = Rss / pairs is theirs, and
+        ``hidden_pairs`` counts the rest.
         smoothed=True: the statistics of the smoothed posterior (:meth:`smooth`):
         its means and marginals in place of the fit's, and its lag-one
         cross-covariances added into A10."""
@@ -473,6 +511,8 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         stats = mstep.combine(state, dyad)
         if eng.p:   # covariates: G, H and the beta the residual Yt was taken at
             stats.update(mstep.combine_covar(*eng.covar_stats(), eng.beta))
+        if eng.masked:   # Rss and pairs run over the observed pairs only
+            stats["hidden_pairs"] = float(sum(eng.hidden_pairs))
         return stats
 
     def _model_params64(self) -> dict:
@@ -540,6 +580,8 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         the statistics)."""
         if smoothed and self._time_sharded():
             raise NotImplementedError("smoothed=True is not available on a time-sharded run")
+        if smoothed and getattr(self.model, "missing", None) is not None:
+            raise NotImplementedError("smoothed=True is not available with missing dyads")
         em = self.history.setdefault("em", [])
         for k in range(int(n_rounds)):
             self.fit(max_iter=inner_iter, tolerance=tolerance, verbose=False)

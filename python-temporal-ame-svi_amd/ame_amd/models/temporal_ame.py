@@ -107,6 +107,33 @@ class TemporalAMEModel:
         # dyadic covariates (extension, set_covariates): none by default
         self.W: Optional[torch.Tensor] = None
         self.beta: Optional[torch.Tensor] = None
+        # hidden dyads (extension, set_missing): none by default
+        self.missing: Optional[torch.Tensor] = None
+
+    def set_missing(self, mask) -> None:
+        """Mark dyads as unobserved (the reference has no such notion).  ``mask``
+        is (n, n, T), bool or uint8, True = hidden; the unit is the unordered
+        pair, so ``mask[i, j, t] == mask[j, i, t]`` is required (the diagonal is
+        ignored).  ``None`` clears the mask.  ``Y`` stays finite everywhere: a
+        fit never reads the values under the mask, which may be held-out truth
+        (``predictive_check(subset="held_out")`` scores them) or anything else.
+        Set the mask before a VI object is built on the model."""
+        if mask is None:
+            self.missing = None
+            return
+        m = torch.as_tensor(mask)
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"mask has dtype {m.dtype}, expected bool or uint8")
+        if tuple(m.shape) != (self.n, self.n, self.T):
+            raise ValueError(f"mask has shape {tuple(m.shape)}, expected ({self.n}, {self.n}, {self.T})")
+        m = (m != 0).detach().to("cpu").clone()
+        idx = torch.arange(self.n)
+        m[idx, idx] = False
+        if not torch.equal(m, m.transpose(0, 1)):
+            bad = int((m != m.transpose(0, 1)).sum()) // 2
+            raise ValueError(f"mask is not symmetric: {bad} pair(s) with mask[i, j, t] != mask[j, i, t] "
+                             "(the unit is the unordered pair)")
+        self.missing = m.contiguous()
 
     MAX_COVARIATES = 8   # AME_MAX_COVARIATES of include/ame_amd.h
 
