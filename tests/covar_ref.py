@@ -1,6 +1,6 @@
 """fp64 numpy reference of the dyadic-covariate regression term (test-only;
 imports nothing from ame_amd except in make_model / cpu_runs, which build the
-end-to-end case).
+end-to-end case, and through gpu_inputs' network).
 
     y_ij,t = mu_ij,t + sum_k beta_k w_k,ij,t + eps,   eps ~ N(0, R)
 
@@ -32,6 +32,18 @@ def make_w(n, T, p, seed=0):
     W[:, iu[0], iu[1]] = w
     W[:, iu[1], iu[0]] = w[..., ::-1]
     return W
+
+
+def gpu_inputs(case):
+    """(X, Y, W, beta) of a direct kernel case (n, T, r, p) of
+    tests/test_gpu_covar.py: make_state's means, mstep_ref.gpu_network's network,
+    make_w's covariates and a beta of scale 0.5.  What its _Device uploads, and
+    what tests/test_covar_ref.py measures the reference's sensitivity on."""
+    import predictive_ref as PR
+    n, T, r, p = case
+    X, _ = PR.make_state(n, T, r)
+    beta = np.random.default_rng(p + n).standard_normal(p) * 0.5
+    return X, M.gpu_network(n, T, r), make_w(n, T, p), beta
 
 
 def effect(W, beta):

@@ -1,6 +1,7 @@
 """fp64 numpy reference of the M-step of variational EM: the sufficient
 statistics of q, the closed-form maximisers and the objective F (test-only;
-imports nothing from ame_amd).  V0 and C01 come from predictive_ref.moments.
+imports nothing from ame_amd except in gpu_network, which generates the GPU
+tests' network).  V0 and C01 come from predictive_ref.moments.
 
 q(x_it) = N(m_it, S_it), independent across nodes and time; E_it = m_it m_it' + S_it.
 
@@ -57,6 +58,16 @@ def dyad_rows(X, S, r, Y):
         mag[t] = (len(iu[0]), (e[:, 0] ** 2 + np.abs(v00)).sum(), (e[:, 1] ** 2 + np.abs(v11)).sum(),
                   (np.abs(e[:, 0] * e[:, 1]) + np.abs(c)).sum())
     return rows, mag
+
+
+def gpu_network(n, T, r):
+    """The network (n, n, T, 2), fp32, of the direct kernel cases of
+    tests/test_gpu_mstep.py and tests/test_gpu_covar.py: what their _Device
+    packs, and what the CPU tests of the references' sensitivity read."""
+    from ame_amd import TemporalAMEModel
+    m = TemporalAMEModel(n, T, r, seed=5)
+    m.generate_data_fast(seed=9)
+    return np.ascontiguousarray(m.Y.numpy(), dtype=np.float32)
 
 
 def combine(srows, drows):

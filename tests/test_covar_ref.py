@@ -20,6 +20,7 @@ import torch
 import covar_ref as CR
 import mstep_ref as M
 import predictive_ref as PR
+import test_gpu_covar as G
 
 EPS = 2.0 ** -52
 
@@ -106,6 +107,65 @@ def test_rss_identity_equals_recomputed_residuals(seed):
     err = np.abs(got - want)
     print(f"max err / (N 2^-52 Sigma) = {(err / (N * EPS * sig)).max():.3e}")
     assert (err <= N * EPS * sig).all()
+
+
+# The inputs of the cases test_gpu_covar.py added for every compiled r and p: on
+# these the G bound (5e-6 x sum|w_a||e_b|) must still separate fp32 arithmetic
+# from a wrong kernel.
+GPU_NEW_CASES = G.EVERY_R_P + G.SMALL_P
+
+
+def _mean_mu_f32(X_t, r):
+    """covar_ref.mean_mu in np.float32: a_i, b_j and the r products u_ik v_jk,
+    each rounded, summed one after another (np.cumsum is sequential)."""
+    X_t = np.asarray(X_t, np.float32)
+    n = X_t.shape[0]
+    a, b, u, v = X_t[:, 0], X_t[:, 1], X_t[:, 2:2 + r], X_t[:, 2 + r:2 + 2 * r]
+    terms = np.concatenate([np.broadcast_to(a[:, None, None], (n, n, 1)),
+                            np.broadcast_to(b[None, :, None], (n, n, 1)), u[:, None, :] * v[None, :, :]], axis=-1)
+    assert terms.dtype == np.float32
+    m0 = np.cumsum(terms, axis=-1, dtype=np.float32)[..., -1]
+    return np.stack([m0, m0.T], axis=-1)
+
+
+def _g_rows_f32(X, r, Yres, W):
+    """G of covar_ref.gh_rows with e formed in fp32 (fp32 means, fp32
+    subtraction from the fp32 residual network) and the sums in fp64, the split
+    of precisions the device makes."""
+    p, n, _, T, _ = W.shape
+    iu = np.triu_indices(n, 1)
+    G_ = np.zeros((T, p, 2, 2))
+    for t in range(T):
+        e = (np.asarray(Yres[:, :, t], np.float32) - _mean_mu_f32(X[:, t], r))[iu[0], iu[1]]
+        assert e.dtype == np.float32
+        G_[t] = np.einsum("kna,nb->kab", W[:, iu[0], iu[1], t].astype(np.float64), e.astype(np.float64))
+    return G_
+
+
+@pytest.mark.parametrize("case", GPU_NEW_CASES, ids=G.IDS)
+def test_gpu_G_bound_passes_fp32_and_shows_a_dropped_column(case):
+    """(a) G evaluated with fp32 means and residuals stays within one tenth of
+    the bound (a condition on the inputs: if a seed breaks it, change the input,
+    not the bound; measured worst over these cases 1.7e-8 of sum|w_a||e_b| at
+    n = 20 and 6.8e-9 at n = 65, bound 5e-6: were the rule ever tightened, this
+    is the room it has).
+    (b) With the last latent column u_{r-1} zeroed, the column next to the K
+    zero padding of the kernel's Ma / Mb rows, in every slice at least one entry
+    of G moves by at least 10 x its bound (measured: 751 x at the least)."""
+    n, T, r, p = case
+    X, Y, W, beta = CR.gpu_inputs(case)
+    Yres = CR.resid(Y, W, beta)
+    G64, Gm, _, _ = CR.gh_rows(X, r, Yres, W)
+    bound = 5e-6 * Gm
+    dev = np.abs(_g_rows_f32(X, r, Yres, W) - G64)
+    print(f"(a) fp32 evaluation: max deviation / sum|w_a||e_b| = {(dev / Gm).max():.3e} (bound 5e-6)")
+    assert (dev <= 0.1 * bound).all(), (dev / bound).max()
+    Xd = X.copy()
+    Xd[:, :, 2 + r - 1] = 0.0
+    moved = np.abs(CR.gh_rows(Xd, r, Yres, W)[0] - G64) / bound
+    per_slice = moved.reshape(T, -1).max(1)
+    print(f"(b) u_(r-1) dropped: largest move / bound per slice, the least = {per_slice.min():.1f}")
+    assert (per_slice >= 10.0).all(), per_slice
 
 
 def test_solve_without_beta_is_unchanged():

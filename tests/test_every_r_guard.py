@@ -111,3 +111,70 @@ def test_predictive_tests_cover_every_r():
         assert set(shapes) == set(R.GPU_SHAPES) | set(R.GPU_SHAPES_EVERY_R)
     # DELTA0 is measured over the same inputs
     assert set(M.DELTA0_SHAPES) == set(R.GPU_SHAPES) | set(R.GPU_SHAPES_EVERY_R)
+
+
+def mstep_state_k(r):
+    """The instance of ame_mstep_state_kernel<K> that serves r, restated from
+    ame_mstep_state_dispatch (csrc/ame_mstep.hip): the first of K = 1, 2, 5, 10,
+    18 with 256 K >= d^2, d = 2 + 2 r."""
+    need = -(-(2 + 2 * r) ** 2 // 256)
+    return next(k for k in (1, 2, 5, 10, 18) if need <= k)
+
+
+def test_em_kernel_tests_cover_every_instance():
+    """The M-step, covariate and missing-dyad kernels: every instance per r
+    (ame_predict_pairs_kernel<R, 2>, the mask selector of <R, 0> / <R, 2>, the K
+    loop counts of ame_covar_g_kernel and ame_fill_kernel), per K
+    (ame_mstep_state_kernel<K>) and per p (ame_covar_{g,h,resid}_kernel<P>)."""
+    import test_gpu_covar as CV
+    import test_gpu_missing as MS
+    import test_gpu_mstep as MT
+    import test_covar_ref as CVR
+    import test_mstep_ref as MTR
+    # M-step
+    for fn in (MT.test_state_rows_match_fp64_reference, MT.test_dyad_rows_match_reference_and_ame_predict,
+               MT.test_bit_identity):
+        shapes = _params(fn, "shape")
+        assert {s[2] for s in shapes} == ALL_R, fn.__name__
+        assert (63, 3, 20) in shapes and len(set(shapes)) == len(shapes), fn.__name__
+        assert set(shapes) >= {(65, 2, r) for r in ALL_R - {1, 2, 3, 5, 8, 16, 20, 32}}, fn.__name__
+    assert (63 % 32, 65 % 32) == (31, 1)           # the chunk that stops the prefetch one short; a one-node chunk
+    fitted = _params(MT.test_statistics_of_a_fitted_state, "method,T,r")
+    assert {m for m, _, r in fitted if r == 3} == VARIANTS and ("good", 3, 20) in fitted
+    # the instance map the list rests on: if the thresholds of the dispatch move,
+    # these are the r to look at again
+    assert [mstep_state_k(r) for r in (1, 7, 8, 10, 11, 16, 17, 24, 25, 32)] == [1, 1, 2, 2, 5, 5, 10, 10, 18, 18]
+    assert {mstep_state_k(r) for r in ALL_R} == {1, 2, 5, 10, 18}
+    assert {r for r in ALL_R if mstep_state_k(r) == 10} == set(range(17, 25))
+    assert (2 + 2 * 7) ** 2 == 256 and (2 + 2 * 24) ** 2 == 2500 and (2 + 2 * 32) ** 2 <= 18 * 256
+    # covariates
+    for fn in (CV.test_H_matches_fp64_reference, CV.test_G_matches_fp64_reference,
+               CV.test_slice_split_invariance, CV.test_resid_is_fp64_rounded_once):
+        cases = _params(fn, "case")
+        assert len(set(cases)) == len(cases), fn.__name__
+        assert {c[2] for c in cases} == ALL_R, fn.__name__
+        assert set(cases) >= {(65, 2, r, 1 + (r - 1) % 8) for r in ALL_R}, fn.__name__
+        for p in range(1, 9):
+            assert len({(n, T) for n, T, _, pp in cases if pp == p}) >= 2, (fn.__name__, p)
+        # every MFMA step count of the G kernel's K loop, pad4(r + 2) / 4
+        assert {(r + 2 + 3) // 4 for _, _, r, _ in cases} == set(range(1, 10))
+    # missing dyads
+    for fn in (MS.test_fill_writes_hidden_entries_only, MS.test_fill_correction_sums,
+               MS.test_predict_and_mstep_select_pairs):
+        cases = _params(fn, "case")
+        assert len(set(cases)) == len(cases), fn.__name__
+        assert {c[2] for c in cases} == ALL_R, fn.__name__
+        assert set(cases) >= set(MS.CASES) | {(65, 3, r) for r in ALL_R - {1, 2, 3, 16, 32}}, fn.__name__
+    assert {(r + 3) // 4 for r in ALL_R} == set(range(1, 9))      # the fill kernel's K loop counts
+    for case in MS.EVERY_R:
+        assert MS.fill_masks(case, ()) == ("random30", "cols63_64", "tile")
+        assert MS.select_masks(case) == ("random30",)
+        assert set(MS.fill_masks(case, ())) <= set(MS.masks_for(*case[:2]))
+    for case in MS.CASES:   # the hand-picked cases keep every mask
+        names = tuple(MS.masks_for(*case[:2]))
+        assert MS.fill_masks(case, names) == names
+        assert set(names) - {"cols63_64"} <= set(MS.select_masks(case)) <= set(names)
+    # the references' sensitivity (test_mstep_ref.py, test_covar_ref.py) is
+    # measured over the inputs of the new cases
+    assert set(MTR.GPU_NEW_SHAPES) == {(63, 3, 20)} | set(MT.EVERY_R)
+    assert set(CVR.GPU_NEW_CASES) == set(CV.EVERY_R_P) | set(CV.SMALL_P)

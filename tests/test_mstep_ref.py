@@ -13,6 +13,7 @@ import pytest
 
 import mstep_ref as M
 import predictive_ref as PR
+import test_gpu_mstep as G
 
 SHAPES = ((12, 4, 2), (9, 3, 1), (20, 2, 3))
 
@@ -147,6 +148,61 @@ def test_rss_diagonal_is_sq_err_plus_mean_var(shape):
         assert abs(rows[t, 2] - (sums[8] + sums[6])) <= 1e-12 * abs(rows[t, 2])
     assert abs(st["Rss"][0, 0] - rows[:, 1].sum()) <= 1e-12 * st["Rss"][0, 0]
     assert st["Rss"][0, 1] == st["Rss"][1, 0]
+
+
+# The inputs of the cases test_gpu_mstep.py added for every compiled r: on these
+# the dyad bounds (Rss00 / Rss11 5e-6 relative, Rss01 5e-6 x sum|summand|) must
+# still separate fp32 arithmetic from a wrong kernel.
+GPU_NEW_SHAPES = ((63, 3, 20),) + G.EVERY_R
+
+
+def _dyad_rows_f32(X, S, r, Y):
+    """mstep_ref.dyad_rows with the per-dyad quantities evaluated in np.float32
+    (predictive_ref.moments_f32: every product rounded, summed one after another;
+    e = y - mean an fp32 subtraction) and the sums over the pairs in fp64, the
+    split of precisions the device makes."""
+    n, T, _ = X.shape
+    iu = np.triu_indices(n, 1)
+    rows = np.zeros((T, 4))
+    for t in range(T):
+        mean0, V0, C01 = PR.moments_f32(X[:, t], S[:, t], r)
+        y = np.asarray(Y[:, :, t], np.float32)
+        e0 = (y[..., 0] - mean0)[iu].astype(np.float64)
+        e1 = (y[..., 1] - mean0.T)[iu].astype(np.float64)
+        v00, v11, c = (a.astype(np.float64) for a in (V0[iu], V0.T[iu], C01[iu]))
+        rows[t] = (len(iu[0]), (e0 ** 2 + v00).sum(), (e1 ** 2 + v11).sum(), (e0 * e1 + c).sum())
+    return rows
+
+
+def _rss_bounds(rows, mag):
+    """The allowance of test_gpu_mstep.py per slice for Rss00, Rss11, Rss01."""
+    return 5e-6 * np.stack([np.abs(rows[:, 1]), np.abs(rows[:, 2]), mag[:, 3]], axis=1)
+
+
+@pytest.mark.parametrize("shape", GPU_NEW_SHAPES, ids=G.IDS)
+def test_gpu_dyad_bounds_pass_fp32_and_show_a_dropped_column(shape):
+    """(a) The reference evaluated in fp32 stays within one tenth of each bound
+    (a condition on the inputs: if a seed breaks it, change the input, not the
+    bound; measured worst over these shapes 2.7e-3 of a bound, which is 1.3e-8
+    relative against the 5e-6 allowed: were the rule ever tightened, this is the
+    room it has).
+    (b) With the last latent column u_{r-1} zeroed, the column next to the K
+    zero padding that an off-by-one in the padding would lose, Rss00, Rss11 and
+    Rss01 of every slice move by at least 10 x their bounds (measured: 26.8 x at
+    the least)."""
+    n, T, r = shape
+    X, S = PR.make_state(n, T, r)
+    Y = M.gpu_network(n, T, r)
+    rows, mag = M.dyad_rows(X, S, r, Y)
+    bound = _rss_bounds(rows, mag)
+    dev = np.abs(_dyad_rows_f32(X, S, r, Y)[:, [1, 2, 3]] - rows[:, [1, 2, 3]])
+    print(f"(a) fp32 evaluation: max deviation / bound = {(dev / bound).max():.3e}")
+    assert (dev <= 0.1 * bound).all(), (dev / bound).max()
+    Xd = X.copy()
+    Xd[:, :, 2 + r - 1] = 0.0
+    moved = np.abs(M.dyad_rows(Xd, S, r, Y)[0][:, [1, 2, 3]] - rows[:, [1, 2, 3]])
+    print(f"(b) u_(r-1) dropped: min move / bound = {(moved / bound).min():.1f}")
+    assert (moved >= 10.0 * bound).all(), (moved / bound).min()
 
 
 def test_statistics_definitions():
