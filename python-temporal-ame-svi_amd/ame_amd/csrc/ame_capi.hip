@@ -4,7 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "ame_common.h"
+#include "ame_tile.h"
 
 int ame_sweep_dispatch(const ame_dims*, const ame_sweep_args*, hipStream_t);
 int ame_sweep_blocks_per_cu(int n, int r, int mode);
@@ -98,6 +98,15 @@ const char* ame_version(void) { return "ame_amd 0.4 gfx950 src=" AME_SRC_HASH; }
 
 // test hook (not in the header): the GEMV-worker partial tag (ame_common.h)
 unsigned int ame_debug_gw_tag(unsigned int epoch, int m) { return ame_gw_tag(epoch, m); }
+// test hooks (not in the header): ame_tile.h's tile enumeration (returns the
+// tile count of n) and slice mapping, run on the host
+long long ame_debug_tri_tile(int tile, int n, int* I0, int* J0) {
+    ame_tri_tile_origin(tile, n, *I0, *J0);
+    return ame_tri_tiles(n);
+}
+void ame_debug_slice_block(int b, int S, int per_slice, int* tl, int* item) {
+    ame_slice_block(b, S, per_slice, *tl, *item);
+}
 
 int ame_supported_r(int* out, int cap) {
     int c = 0;

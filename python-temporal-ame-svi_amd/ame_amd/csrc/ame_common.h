@@ -310,6 +310,12 @@ __host__ __device__ inline long long ame_v2_arr_doubles(const ame_dims* d) {
 #endif
 #define AME_MAX_R 32
 
+// Covariate counts compiled into the library: 1 .. AME_MAX_COVARIATES
+#define AME_FOR_EACH_P(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+#define AME_P_LISTED(PP) +(PP >= 1 && PP <= AME_MAX_COVARIATES)
+static_assert(0 AME_FOR_EACH_P(AME_P_LISTED) == AME_MAX_COVARIATES, "AME_FOR_EACH_P must list 1 .. AME_MAX_COVARIATES");
+#undef AME_P_LISTED
+
 // entry-point names of a split part, and code that only part 0 carries
 #define AME_PFN_CAT2(a, b) a##_p##b
 #define AME_PFN_CAT(a, b) AME_PFN_CAT2(a, b)

@@ -11,49 +11,24 @@
 //    triangle, diagonal tiles included).  The tile's node rows are staged in
 //    LDS as Ma = [a, 1, u] and Mb = [1, b, v] (K zero-padded to a multiple of 4)
 //    and the two products Ma_I.Mb_J' = E[mu_ij[0]], Mb_I.Ma_J' = E[mu_ij[1]] run
-//    on v_mfma_f32_16x16x4_f32, ame_predict's tile and accumulator layout: wave
-//    w holds rows 16 w .. 16 w + 15 of the tile, 16 dyads per lane.  e is formed
-//    in fp32 from the Yt tile (0 where i >= j or beyond n); the P covariate
-//    tiles are read once each and w[a] e[b] is accumulated in fp64 registers
-//    (products of fp32 values are exact in fp64).
+//    on v_mfma_f32_16x16x4_f32 (ame_tile.h: tile order, lane -> dyad layout,
+//    small-K strip product), 16 dyads per lane.  e is formed in fp32 from the
+//    Yt tile (0 where i >= j or beyond n); the P covariate tiles are read once
+//    each and w[a] e[b] is accumulated in fp64 registers (products of fp32
+//    values are exact in fp64).
 // K1h ame_covar_h_kernel<P>: the same tiles for H, without the means; see there.
-// K2 ame_covar_final_kernel: one thread per statistic adds a slice's tile
-//    partials in tile order.
+// K2 ame_col_sum_kernel (ame_tile.h): one thread per statistic adds a slice's
+//    tile partials in tile order, G and H each in a launch of their own.
 // K3 ame_covar_resid_kernel: Yt = Yt_raw - sum_k beta_k Wt[k], elementwise over
 //    the packed layout, float4 per thread, fp64 with every product and sum
 //    rounded on its own, one rounding to fp32.
 // The tile size is a constant and every sum has a fixed order: a slice's row has
 // the same bits under any split of the slices over calls.  No atomics, no
 // waits, nothing of size n^2 written by K1 / K2.
-#include "ame_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define AME_CV_T 64                                   // dyad tile edge
-#define AME_CV_MAXK ((AME_MAX_R + 2 + 3) & ~3)        // 36: padded K of the mean products
-#define AME_CV_LD 38   // LDS row stride: 6 li + lq hits 32 distinct banks per half wave
-static_assert(AME_CV_MAXK <= AME_CV_LD, "a padded mean row must fit the LDS row stride");
-// The Ma / Mb rows are staged here from the means themselves: ame_common.h and
-// ame_wave.h hold no tile-staging helper (ame_predict and ame_elbo stage inside
-// their own kernels, from feature rows a kernel of theirs wrote first), and K is
-// at most 36 floats, so there is no chunk loop to share either.
+#include "ame_tile.h"
 
 // doubles of one partial / output row: G (4 p) then H (4 p^2)
 __host__ __device__ constexpr int ame_covar_row(int p) { return 4 * p + 4 * p * p; }
-
-static inline long long covar_tri_tiles(int n) {
-    const long long nb = (n + AME_CV_T - 1) / AME_CV_T;
-    return nb * (nb + 1) / 2;
-}
-
-// upper-triangle tiles, row-major: (0,0) (0,1) .. (1,1) ..
-__device__ __forceinline__ void covar_tile_origin(int tile, int n, int& I0, int& J0) {
-    const int nb = (n + AME_CV_T - 1) / AME_CV_T;
-    int I = 0, rem = tile;
-    while (rem >= nb - I) { rem -= nb - I; ++I; }
-    I0 = I * AME_CV_T;
-    J0 = (I + rem) * AME_CV_T;
-}
 
 template <int P>
 __global__ void __launch_bounds__(AME_NT)
@@ -61,16 +36,15 @@ ame_covar_g_kernel(const float* __restrict__ x, const float* __restrict__ Yt,
                    const float* __restrict__ Wt, int n, int r, int T_local, int ntile,
                    double* __restrict__ partial) {
     constexpr int NG = 4 * P;
-    __shared__ float MaI[AME_CV_T * AME_CV_LD], MbI[AME_CV_T * AME_CV_LD];
-    __shared__ float MaJ[AME_CV_T * AME_CV_LD], MbJ[AME_CV_T * AME_CV_LD];
+    __shared__ float MaI[AME_DT * AME_SK_LD], MbI[AME_DT * AME_SK_LD];
+    __shared__ float MaJ[AME_DT * AME_SK_LD], MbJ[AME_DT * AME_SK_LD];
     __shared__ double red[4 * NG];
 
     const int tl = blockIdx.x / ntile, tile = blockIdx.x - tl * ntile;
     int I0, J0;
-    covar_tile_origin(tile, n, I0, J0);
-    const int d = 2 + 2 * r, mp = (r + 2 + 3) & ~3;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int li = lane & 15, lq = lane >> 4;
+    ame_tri_tile_origin(tile, n, I0, J0);
+    const int d = 2 + 2 * r, mp = ame_pad4(r + 2);
+    const AmeLaneDyad ld(I0, J0);
 
     // stage Ma = [a, 1, u, 0..], Mb = [1, b, v, 0..] of the tile's row and column nodes
     {
@@ -91,10 +65,10 @@ ame_covar_g_kernel(const float* __restrict__ x, const float* __restrict__ Yt,
             }
             if (ni >= n) ai = bi = 0.f;
             if (nj >= n) aj = bj = 0.f;
-            MaI[row * AME_CV_LD + c] = ai;
-            MbI[row * AME_CV_LD + c] = bi;
-            MaJ[row * AME_CV_LD + c] = aj;
-            MbJ[row * AME_CV_LD + c] = bj;
+            MaI[row * AME_SK_LD + c] = ai;
+            MbI[row * AME_SK_LD + c] = bi;
+            MaJ[row * AME_SK_LD + c] = aj;
+            MbJ[row * AME_SK_LD + c] = bj;
         }
     }
     __syncthreads();
@@ -102,27 +76,22 @@ ame_covar_g_kernel(const float* __restrict__ x, const float* __restrict__ Yt,
     // The wave's 16 x 64 strip goes by 16 x 16 blocks (s): the block's two MFMA
     // products, then its 4 dyads per lane.  The s loop is not unrolled, so the
     // loads in flight are one block's (4 (P + 1) float2 per lane).
-    // accumulator element g of this lane: i = I0 + 16 w + 4 lq + g, j = J0 + 16 s + li
     const int ny = ame_ystride(n);
     const size_t plane = (size_t)T_local * n * ny * 2;   // floats of one packed plane
     const size_t sbase = (size_t)tl * n * ny * 2;
-    const int ro = (16 * w + li) * AME_CV_LD + lq;
+    const int ro = ld.i_op(AME_SK_LD);
     double acc[NG];
 #pragma unroll
     for (int q = 0; q < NG; ++q) acc[q] = 0.0;
 #pragma unroll 1
     for (int s = 0; s < 4; ++s) {
-        const int j = J0 + 16 * s + li;
-        f32x4 m0 = f32x4{0.f, 0.f, 0.f, 0.f}, m1 = m0;
-        const int co = (16 * s + li) * AME_CV_LD + lq;
-        for (int kk = 0; kk < (mp >> 2); ++kk) {
-            m0 = __builtin_amdgcn_mfma_f32_16x16x4f32(MaI[ro + 4 * kk], MbJ[co + 4 * kk], m0, 0, 0, 0);
-            m1 = __builtin_amdgcn_mfma_f32_16x16x4f32(MbI[ro + 4 * kk], MaJ[co + 4 * kk], m1, 0, 0, 0);
-        }
+        const int j = ld.j(s);
+        f32x4 m0, m1;
+        ame_smallk_products(MaI, MbJ, MbI, MaJ, ro, ld.j_op(s, AME_SK_LD), mp >> 2, m0, m1);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int i = I0 + 16 * w + 4 * lq + g;
-            const bool ok = i < n && j < n && i < j;
+            const int i = ld.i(g);
+            const bool ok = ame_upper_pair(i, j, n);
             const size_t o = sbase + ((size_t)(ok ? i : 0) * ny + (ok ? j : 0)) * 2;
             float2 wk[P];
 #pragma unroll
@@ -167,9 +136,8 @@ ame_covar_h_kernel(const float* __restrict__ Wt, int n, int T_local, int ntile,
     __shared__ double red[4 * NH];
     const int tl = blockIdx.x / ntile, tile = blockIdx.x - tl * ntile;
     int I0, J0;
-    covar_tile_origin(tile, n, I0, J0);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int li = lane & 15, lq = lane >> 4;
+    ame_tri_tile_origin(tile, n, I0, J0);
+    const AmeLaneDyad ld(I0, J0);
     const int ny = ame_ystride(n);
     const size_t plane = (size_t)T_local * n * ny * 2;
     const size_t sbase = (size_t)tl * n * ny * 2;
@@ -181,11 +149,11 @@ ame_covar_h_kernel(const float* __restrict__ Wt, int n, int T_local, int ntile,
         for (int q = 0; q < NH; ++q) acc[q] = 0.0;
 #pragma unroll 1
         for (int s = 0; s < 4; ++s) {
-            const int j = J0 + 16 * s + li;
+            const int j = ld.j(s);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int i = I0 + 16 * w + 4 * lq + g;
-                const bool ok = i < n && j < n && i < j;
+                const int i = ld.i(g);
+                const bool ok = ame_upper_pair(i, j, n);
                 const size_t o = sbase + ((size_t)(ok ? i : 0) * ny + (ok ? j : 0)) * 2;
                 float2 wk = *(const float2*)(Wt + k * plane + o);
                 if (!ok) wk = make_float2(0.f, 0.f);
@@ -220,23 +188,6 @@ ame_covar_h_kernel(const float* __restrict__ Wt, int n, int T_local, int ntile,
         }
         __syncthreads();   // `red` is reused by the next row block
     }
-}
-
-// G[tl][q] (q < ng) and H[tl][q - ng]: a slice's tile partials in tile order
-static __global__ void __launch_bounds__(AME_NT)
-ame_covar_final_kernel(const double* __restrict__ partial, int ntile, int ng, int row, long long total,
-                       double* __restrict__ G, double* __restrict__ H) {
-    const long long t = (long long)blockIdx.x * AME_NT + threadIdx.x;
-    if (t >= total) return;
-    const long long tl = t / row;
-    const int q = (int)(t - tl * row);
-    const bool isg = q < ng;
-    if (isg ? G == nullptr : H == nullptr) return;
-    const double* p = partial + (size_t)tl * ntile * row + q;
-    double s = 0.0;
-    for (int b = 0; b < ntile; ++b) s += p[(size_t)b * row];
-    if (isg) G[tl * ng + q] = s;
-    else H[tl * (row - ng) + (q - ng)] = s;
 }
 
 struct CovarBeta {
@@ -285,10 +236,10 @@ ame_covar_resid_kernel(const float4* __restrict__ Yraw, const float4* __restrict
 }
 
 long long ame_covar_work_doubles(const ame_dims* dm, int p) {
-    return (long long)dm->T_local * covar_tri_tiles(dm->n) * ame_covar_row(p);
+    return (long long)dm->T_local * ame_tri_tiles(dm->n) * ame_covar_row(p);
 }
 
-long long ame_covar_blocks(const ame_dims* dm) { return (long long)dm->T_local * covar_tri_tiles(dm->n); }
+long long ame_covar_blocks(const ame_dims* dm) { return (long long)dm->T_local * ame_tri_tiles(dm->n); }
 
 // float4 elements of one packed plane (ny is even: a plane is whole float4s)
 long long ame_covar_plane4(const ame_dims* dm) {
@@ -307,22 +258,17 @@ static void launch_covar_tile(const ame_dims* dm, const ame_covar_args* a, int n
 }
 
 int ame_covar_stats_dispatch(const ame_dims* dm, const ame_covar_args* a, hipStream_t st) {
-    const int ntile = (int)covar_tri_tiles(dm->n), p = a->p;
+    const int ntile = (int)ame_tri_tiles(dm->n), p = a->p;
     switch (p) {
-        case 1: launch_covar_tile<1>(dm, a, ntile, st); break;
-        case 2: launch_covar_tile<2>(dm, a, ntile, st); break;
-        case 3: launch_covar_tile<3>(dm, a, ntile, st); break;
-        case 4: launch_covar_tile<4>(dm, a, ntile, st); break;
-        case 5: launch_covar_tile<5>(dm, a, ntile, st); break;
-        case 6: launch_covar_tile<6>(dm, a, ntile, st); break;
-        case 7: launch_covar_tile<7>(dm, a, ntile, st); break;
-        case 8: launch_covar_tile<8>(dm, a, ntile, st); break;
+#define X(PP) \
+    case PP: launch_covar_tile<PP>(dm, a, ntile, st); break;
+        AME_FOR_EACH_P(X)
+#undef X
         default: return -1;
     }
-    const int row = ame_covar_row(p);
-    const long long total = (long long)dm->T_local * row;
-    hipLaunchKernelGGL(ame_covar_final_kernel, dim3((unsigned)((total + AME_NT - 1) / AME_NT)), dim3(AME_NT),
-                       0, st, a->work, ntile, 4 * p, row, total, a->G, a->H);
+    const int row = ame_covar_row(p), ng = 4 * p;
+    if (a->G) ame_col_sum(a->work, ntile, row, 0, ng, dm->T_local, a->G, st);
+    if (a->H) ame_col_sum(a->work, ntile, row, ng, row - ng, dm->T_local, a->H, st);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -332,16 +278,15 @@ int ame_covar_resid_dispatch(const ame_dims* dm, const float* Yraw, const float*
     for (int k = 0; k < AME_MAX_COVARIATES; ++k) b.b[k] = k < p ? beta[k] : 0.0;
     const long long plane4 = ame_covar_plane4(dm);
     const unsigned grid = (unsigned)((plane4 + AME_NT - 1) / AME_NT);
-#define AME_CV_RESID(PP)                                                                              \
+    switch (p) {
+#define X(PP)                                                                                         \
     case PP:                                                                                          \
         hipLaunchKernelGGL(ame_covar_resid_kernel<PP>, dim3(grid), dim3(AME_NT), 0, st,               \
                            (const float4*)Yraw, (const float4*)Wt, b, plane4, (float4*)out);          \
         break;
-    switch (p) {
-        AME_CV_RESID(1) AME_CV_RESID(2) AME_CV_RESID(3) AME_CV_RESID(4)
-        AME_CV_RESID(5) AME_CV_RESID(6) AME_CV_RESID(7) AME_CV_RESID(8)
+        AME_FOR_EACH_P(X)
+#undef X
         default: return -1;
     }
-#undef AME_CV_RESID
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

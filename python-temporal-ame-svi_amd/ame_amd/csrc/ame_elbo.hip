@@ -15,7 +15,7 @@
 // epilogue while the tile's Y bytes stream in once.  When Y is swap-consistent
 // (Y_ji = swap(Y_ij), checked by K0) only the upper-triangle tiles are read and
 // the mirror half of the reconstruction error is counted twice.
-#include "ame_common.h"
+#include "ame_tile.h"
 #include "ame_sweep_dev.h"
 #include <type_traits>
 using namespace ame;
@@ -86,7 +86,6 @@ int ame_pack_dispatch(const float* Y, float* Yt, const ame_dims* dm, unsigned lo
 // ---------------------------------------------------------------------------
 #define AME_TILE 64
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int R>
@@ -100,18 +99,8 @@ ame_pairs_kernel(ame_dims dm, const float* __restrict__ Yt, const float* __restr
     const int n = dm.n;
     const int nb = (n + AME_TILE - 1) / AME_TILE;
     const int nws = swap_mode ? (nb + 1) / 2 : nb;     // workgroups per slice
-    // XCD-aware: workgroup b runs on XCD b % 8; all workgroups of one slice
-    // share an XCD, so its U, V are fetched into one L2 instead of eight
-    const int b = blockIdx.x;
     int tl, s;
-    if ((dm.T_local & 7) == 0) {
-        const int k = b >> 3, q = k / nws;
-        tl = (b & 7) * (dm.T_local >> 3) + q;
-        s = k - q * nws;
-    } else {
-        tl = b / nws;
-        s = b - tl * nws;
-    }
+    ame_slice_block(blockIdx.x, dm.T_local, nws, tl, s);   // XCD-aware (ame_tile.h)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int li = lane & 15, lq = lane >> 4;
 
@@ -326,16 +315,8 @@ ame_pairs2_kernel(ame_dims dm, const float* __restrict__ Yt, const float* __rest
     const int n = dm.n;
     const int nb = (n + AME_TILE - 1) / AME_TILE;
     const int nws = swap_mode ? (nb + 1) / 2 : nb;
-    const int b = blockIdx.x;
     int tl, s;
-    if ((dm.T_local & 7) == 0) {   // XCD-aware, as ame_pairs_kernel
-        const int k = b >> 3, q = k / nws;
-        tl = (b & 7) * (dm.T_local >> 3) + q;
-        s = k - q * nws;
-    } else {
-        tl = b / nws;
-        s = b - tl * nws;
-    }
+    ame_slice_block(blockIdx.x, dm.T_local, nws, tl, s);   // XCD-aware (ame_tile.h)
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 15, lq = lane >> 4;
 

@@ -13,40 +13,30 @@
 //    j >> 6.  Integer counts only: hidden pairs i < j of the slice, observed
 //    partners of the row, entries whose transpose disagrees.
 // K2 ame_fill_kernel: one workgroup per (slice, 64 x 64 tile of the upper
-//    triangle), ame_predict's MODE 0 tile order and XCD mapping.  The tile's 64
+//    triangle), in ame_tile.h's tile order and slice mapping.  The tile's 64
 //    mask words are read first (on a diagonal tile only bits j > i are kept); a
 //    tile with nothing hidden writes zero partials and returns before any mean
 //    is loaded.  Otherwise U and V of the tile's row and column nodes are
 //    staged in LDS (K = r zero-padded to a multiple of 4) and the two products
-//    run on v_mfma_f32_16x16x4_f32 in ame_covar_g_kernel's tile and accumulator
-//    layout; each hidden pair gets its two entries (fp32 adds) and adds its
-//    correction terms in fp64.  No other element of Yt is written.
-// K3 ame_fill_final_kernel: one thread per (slice, statistic) adds the tile
-//    partials in tile order.
+//    run on v_mfma_f32_16x16x4_f32 (ame_tile.h: lane -> dyad layout, small-K
+//    strip product); each hidden pair gets its two entries (fp32 adds) and adds
+//    its correction terms in fp64.  No other element of Yt is written.
+// K3 ame_col_sum_kernel (ame_tile.h): one thread per (slice, statistic) adds the
+//    tile partials in tile order.
 // The tile size is a constant and every sum has a fixed order: a slice's row
 // has the same bits under any split of the slices over calls.  No atomics in
 // the floating-point sums, no waits between workgroups.
-#include "ame_common.h"
+#include "ame_tile.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define AME_MS_T 64     // dyad tile edge = bits of one mask word
-#define AME_MS_LD 38    // LDS row stride (ame_covar.hip: 6 li + lq hits 32 distinct banks per half wave)
 #define AME_MS_NC 2     // correction sums per slice
-static_assert(((AME_MAX_R + 3) & ~3) <= AME_MS_LD, "a padded (U, V) row must fit the LDS row stride");
-
-static inline long long missing_tri_tiles(int n) {
-    const long long nb = (n + AME_MS_T - 1) / AME_MS_T;
-    return nb * (nb + 1) / 2;
-}
 
 long long ame_mask_words_count(const ame_dims* dm) {
-    return (long long)dm->T_local * dm->n * ((dm->n + 63) / 64);
+    return (long long)dm->T_local * dm->n * ame_mask_row_words(dm->n);
 }
 long long ame_fill_work_doubles(const ame_dims* dm) {
-    return (long long)dm->T_local * missing_tri_tiles(dm->n) * AME_MS_NC;
+    return (long long)dm->T_local * ame_tri_tiles(dm->n) * AME_MS_NC;
 }
-long long ame_fill_blocks(const ame_dims* dm) { return (long long)dm->T_local * missing_tri_tiles(dm->n); }
+long long ame_fill_blocks(const ame_dims* dm) { return (long long)dm->T_local * ame_tri_tiles(dm->n); }
 
 // ---------------------------------------------------------------------------
 // K1: pack the mask
@@ -57,7 +47,7 @@ ame_pack_mask_kernel(const uint8_t* __restrict__ M, unsigned long long* __restri
                      unsigned long long* __restrict__ asym) {
     __shared__ unsigned int cnt[3];   // hidden in the row, hidden with j > i, asymmetric
     const int tl = blockIdx.x / n, i = blockIdx.x - tl * n;
-    const int tg = t_begin + tl, nw = (n + 63) >> 6;
+    const int tg = t_begin + tl, nw = ame_mask_row_words(n);
     const int lane = threadIdx.x & 63;
     if (threadIdx.x < 3) cnt[threadIdx.x] = 0u;
     __syncthreads();
@@ -121,36 +111,21 @@ struct FillParams {
 
 __global__ void __launch_bounds__(AME_NT)
 ame_fill_kernel(FillParams p) {
-    __shared__ float UI[AME_MS_T * AME_MS_LD], VI[AME_MS_T * AME_MS_LD];
-    __shared__ float UJ[AME_MS_T * AME_MS_LD], VJ[AME_MS_T * AME_MS_LD];
-    __shared__ float abI[AME_MS_T * 2], abJ[AME_MS_T * 2];
-    __shared__ unsigned long long mw[AME_MS_T];
+    __shared__ float UI[AME_DT * AME_SK_LD], VI[AME_DT * AME_SK_LD];
+    __shared__ float UJ[AME_DT * AME_SK_LD], VJ[AME_DT * AME_SK_LD];
+    __shared__ float abI[AME_DT * 2], abJ[AME_DT * 2];
+    __shared__ unsigned long long mw[AME_DT];
     __shared__ double red[4 * AME_MS_NC];
 
     const int n = p.n, ntile = p.ntile;
-    const int bb = blockIdx.x;
-    int tl, tile;
-    if ((p.S & 7) == 0) {   // blocks that share an XCD share slices (as ame_predict_pairs_kernel)
-        const int k = bb >> 3, q = k / ntile;
-        tl = (bb & 7) * (p.S >> 3) + q;
-        tile = k - q * ntile;
-    } else {
-        tl = bb / ntile;
-        tile = bb - tl * ntile;
-    }
-    int I0, J0;
-    {   // upper-triangle tiles, row-major: (0,0) (0,1) .. (1,1) ..
-        const int nb = (n + AME_MS_T - 1) / AME_MS_T;
-        int I = 0, rem = tile;
-        while (rem >= nb - I) { rem -= nb - I; ++I; }
-        I0 = I * AME_MS_T;
-        J0 = (I + rem) * AME_MS_T;
-    }
+    int tl, tile, I0, J0;
+    ame_slice_block(blockIdx.x, p.S, ntile, tl, tile);
+    ame_tri_tile_origin(tile, n, I0, J0);
     double* out = p.partial + ((size_t)tl * ntile + tile) * AME_MS_NC;
 
     // the tile's mask words: row I0 + k, word J0 >> 6
     bool any = false;
-    if (threadIdx.x < AME_MS_T) {
+    if (threadIdx.x < AME_DT) {
         const int i = I0 + (int)threadIdx.x;
         unsigned long long wd = 0ull;
         if (i < n) {
@@ -167,9 +142,8 @@ ame_fill_kernel(FillParams p) {
         return;
     }
 
-    const int r = p.r, d = 2 + 2 * r, kp = (r + 3) & ~3;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int li = lane & 15, lq = lane >> 4;
+    const int r = p.r, d = 2 + 2 * r, kp = ame_pad4(r);
+    const AmeLaneDyad ld(I0, J0);
     {   // stage (a, b), U, V of the tile's row and column nodes, K zero-padded
         const int row = threadIdx.x >> 2;
         const int ni = I0 + row, nj = J0 + row;
@@ -181,10 +155,10 @@ ame_fill_kernel(FillParams p) {
                 if (ni < n) { ui = xi[2 + c]; vi = xi[2 + r + c]; }
                 if (nj < n) { uj = xj[2 + c]; vj = xj[2 + r + c]; }
             }
-            UI[row * AME_MS_LD + c] = ui;
-            VI[row * AME_MS_LD + c] = vi;
-            UJ[row * AME_MS_LD + c] = uj;
-            VJ[row * AME_MS_LD + c] = vj;
+            UI[row * AME_SK_LD + c] = ui;
+            VI[row * AME_SK_LD + c] = vi;
+            UJ[row * AME_SK_LD + c] = uj;
+            VJ[row * AME_SK_LD + c] = vj;
         }
         if ((threadIdx.x & 3) < 2) {
             const int c = threadIdx.x & 3;
@@ -194,29 +168,24 @@ ame_fill_kernel(FillParams p) {
     }
     __syncthreads();
 
-    // accumulator element g of this lane: i = I0 + 16 w + 4 lq + g, j = J0 + 16 s + li
     float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
-    const int ro = (16 * w + li) * AME_MS_LD + lq;
+    const int ro = ld.i_op(AME_SK_LD);
     double sm[AME_MS_NC] = {0.0, 0.0};
 #pragma unroll 1
     for (int s = 0; s < 4; ++s) {
-        const int cj = 16 * s + li, j = J0 + cj;
+        const int cj = ld.col(s), j = J0 + cj;
         // this lane's four rows: does any hold the bit of column j?  (uniform skip per wave)
         unsigned int bits = 0u;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) bits |= (unsigned int)((mw[16 * w + 4 * lq + g] >> cj) & 1ull) << g;
+        for (int g = 0; g < 4; ++g) bits |= (unsigned int)((mw[ld.row(g)] >> cj) & 1ull) << g;
         if (__ballot(bits != 0u) == 0ull) continue;
-        f32x4 pp = f32x4{0.f, 0.f, 0.f, 0.f}, qq = pp;
-        const int co = cj * AME_MS_LD + lq;
-        for (int kk = 0; kk < (kp >> 2); ++kk) {
-            pp = __builtin_amdgcn_mfma_f32_16x16x4f32(UI[ro + 4 * kk], VJ[co + 4 * kk], pp, 0, 0, 0);
-            qq = __builtin_amdgcn_mfma_f32_16x16x4f32(VI[ro + 4 * kk], UJ[co + 4 * kk], qq, 0, 0, 0);
-        }
+        f32x4 pp, qq;
+        ame_smallk_products(UI, VJ, VI, UJ, ro, ld.j_op(s, AME_SK_LD), kp >> 2, pp, qq);
         const float aj = abJ[cj * 2], bj = abJ[cj * 2 + 1];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int ri = 16 * w + 4 * lq + g, i = I0 + ri;
-            if (((bits >> g) & 1u) && i < n && j < n && i < j) {
+            const int ri = ld.row(g), i = I0 + ri;
+            if (((bits >> g) & 1u) && ame_upper_pair(i, j, n)) {
                 const float ai = abI[ri * 2], bi = abI[ri * 2 + 1];
                 const float pv = pp[g], qv = qq[g];
                 const float2 up = make_float2(ai + pv, bi + qv);
@@ -240,26 +209,14 @@ ame_fill_kernel(FillParams p) {
     }
 }
 
-// K3: corr[tl][q] = a slice's tile partials in tile order
-static __global__ void __launch_bounds__(64)
-ame_fill_final_kernel(const double* __restrict__ partial, int ntile, int total, double* __restrict__ corr) {
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= total) return;
-    const int tl = t / AME_MS_NC, q = t - tl * AME_MS_NC;
-    const double* ps = partial + (size_t)tl * ntile * AME_MS_NC + q;
-    double s = 0.0;
-    for (int b = 0; b < ntile; ++b) s += ps[(size_t)b * AME_MS_NC];
-    corr[t] = s;
-}
-
 int ame_fill_missing_dispatch(const ame_dims* dm, const ame_fill_args* a, hipStream_t st) {
     FillParams p;
     p.n = dm->n;
     p.r = dm->r;
     p.S = dm->T_local;
     p.ny = ame_ystride(dm->n);
-    p.nw = (dm->n + 63) / 64;
-    p.ntile = (int)missing_tri_tiles(dm->n);
+    p.nw = ame_mask_row_words(dm->n);
+    p.ntile = (int)ame_tri_tiles(dm->n);
     p.x = a->x;
     p.Mt = (const unsigned long long*)a->Mt;
     p.Yt = a->Yt;
@@ -269,8 +226,7 @@ int ame_fill_missing_dispatch(const ame_dims* dm, const ame_fill_args* a, hipStr
     p.r11 = a->rinv[3];
     p.partial = a->work;
     hipLaunchKernelGGL(ame_fill_kernel, dim3((unsigned)((long long)p.S * p.ntile)), dim3(AME_NT), 0, st, p);
-    const int total = p.S * AME_MS_NC;
-    hipLaunchKernelGGL(ame_fill_final_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, a->work,
-                       p.ntile, total, a->corr);
+    // K3: corr[tl][q] = a slice's tile partials in tile order
+    ame_col_sum<64>(a->work, p.ntile, AME_MS_NC, 0, AME_MS_NC, p.S, a->corr, st);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

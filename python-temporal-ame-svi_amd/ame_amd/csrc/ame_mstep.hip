@@ -10,13 +10,13 @@
 //    run of d^2 floats read once with coalesced loads (one node prefetched into
 //    registers ahead of the sums).  Every product and every sum is fp64.  The
 //    partials go to `work`.
-// K2 ame_mstep_state_final_kernel: one thread per output element adds the chunk
-//    partials in chunk order.
+// K2 ame_col_sum_kernel (ame_tile.h): one thread per output element adds the
+//    chunk partials in chunk order.
 // The chunk size is a constant, so the summation order of a slice's row does
 // not depend on T_local, t_begin or how the caller splits slices over calls.
 // Bandwidth-bound by design: the covariances are the only large read (4 d^2
 // bytes per node and slice) and nothing of that size is written.
-#include "ame_common.h"
+#include "ame_tile.h"
 
 #define AME_MS_CHUNK 32                      // nodes per workgroup
 #define AME_MS_MAXD (2 + 2 * AME_MAX_R)      // 66
@@ -92,20 +92,6 @@ ame_mstep_state_kernel(const float* __restrict__ x, const float* __restrict__ co
     }
 }
 
-// out[tl][which][e] = sum over chunks, in chunk order
-static __global__ void __launch_bounds__(AME_NT)
-ame_mstep_state_final_kernel(const double* __restrict__ partial, int nchunk, int dd2, long long total,
-                             double* __restrict__ out) {
-    const long long g = (long long)blockIdx.x * AME_NT + threadIdx.x;
-    if (g >= total) return;
-    const long long tl = g / dd2;
-    const int e = (int)(g - tl * dd2);
-    const double* p = partial + (size_t)tl * nchunk * dd2 + e;
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) s += p[(size_t)c * dd2];
-    out[g] = s;
-}
-
 static inline int mstep_chunks(int n) { return (n + AME_MS_CHUNK - 1) / AME_MS_CHUNK; }
 
 long long ame_mstep_state_work_doubles(const ame_dims* dm) {
@@ -131,8 +117,7 @@ int ame_mstep_state_dispatch(const ame_dims* dm, const ame_mstep_args* a, hipStr
     else if (K <= 18) AME_MS_LAUNCH(18);
     else return -1;
 #undef AME_MS_LAUNCH
-    const long long total = (long long)dm->T_local * 2 * dd;
-    hipLaunchKernelGGL(ame_mstep_state_final_kernel, dim3((unsigned)((total + AME_NT - 1) / AME_NT)),
-                       dim3(AME_NT), 0, st, a->work, nchunk, 2 * dd, total, a->state);
+    // out[tl][which][e] = sum over chunks, in chunk order
+    ame_col_sum(a->work, nchunk, 2 * dd, 0, 2 * dd, dm->T_local, a->state, st);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

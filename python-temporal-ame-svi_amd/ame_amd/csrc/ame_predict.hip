@@ -20,29 +20,26 @@
 //
 // K1 ame_predict_feat_kernel: one workgroup per (slice, node) writes the six
 //    segments once (row of PredictCfg<R>::L floats) into `work`.
-// K2 ame_predict_pairs_kernel: one workgroup per (slice, 64 x 64 tile); the
+// K2 ame_predict_pairs_kernel: one workgroup per (slice, 64 x 64 tile; ame_tile.h
+//    holds the tile order, the slice mapping and the lane -> dyad layout); the
 //    five products stream K in chunks of 32 through LDS (both 64-row operand
 //    tiles, next chunk prefetched into registers during the MFMAs), each wave
 //    keeps its 16 x 64 part of the five results in registers (20 accumulators
 //    of 4) and runs the epilogue on them: scoring in fp64 against Y, read once
 //    from the upper triangle (MODE 0, tiles I <= J), or the dense block (MODE 1).
-// K3 ame_predict_final_kernel: fixed-order sum of a slice's tile partials.
-// MODE 2 of K2 (ame_mstep_stats): the same tiles and products, with the M-step's
-//    residual second moments as the epilogue and ame_mstep_dyad_final_kernel as K3.
+// K3 ame_tile_sum_kernel (ame_tile.h): fixed-order sum of a slice's tile partials.
+// MODE 2 of K2 (ame_mstep_stats): the same tiles, products and K3, with the
+//    M-step's residual second moments as the epilogue.
 // No atomics, no spin, no O(n^2) intermediate.
 #include <type_traits>
 
-#include "ame_common.h"
+#include "ame_tile.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define AME_PT 64        // dyad tile edge
 #define AME_PKB 32       // K chunk in floats
 #define AME_PLD 34       // LDS row stride: 2 li + lq hits 32 distinct banks per half wave
 #define AME_PNS AME_PREDICT_SUMS
 #define AME_MS_DYAD 4    // M-step dyad statistics per slice: pairs, Rss00, Rss11, Rss01
 
-__host__ __device__ constexpr int ame_pad4(int k) { return (k + 3) & ~3; }
 // floats of one node's feature row for latent dim r
 __host__ __device__ constexpr int ame_predict_row(int r) {
     return 2 * ame_pad4(r + 2) + 2 * ame_pad4(2 + r * (r + 1) + 2 * r) + 2 * ame_pad4(2 + 4 * r + 2 * r * r);
@@ -165,43 +162,21 @@ ame_predict_pairs_kernel(PredictParams p) {
     using C = PredictCfg<R>;
     constexpr int L = C::L;
     const int n = p.n, ntile = p.ntile;
-    const int bb = blockIdx.x;
-    int tl, tile;
-    if ((p.S & 7) == 0) {   // blocks that share an XCD share slices (as ame_pairs2_kernel)
-        const int k = bb >> 3, q = k / ntile;
-        tl = (bb & 7) * (p.S >> 3) + q;
-        tile = k - q * ntile;
-    } else {
-        tl = bb / ntile;
-        tile = bb - tl * ntile;
-    }
-    int I0, J0, ilim, jlim;
-    if (MODE == 0) {   // upper-triangle tiles, row-major: (0,0) (0,1) .. (1,1) ..
-        const int nb = (n + AME_PT - 1) / AME_PT;
-        int I = 0, rem = tile;
-        while (rem >= nb - I) { rem -= nb - I; ++I; }
-        I0 = I * AME_PT;
-        J0 = (I + rem) * AME_PT;
+    int tl, tile, I0, J0, ilim, jlim;
+    ame_slice_block(blockIdx.x, p.S, ntile, tl, tile);
+    if (MODE != 1) {   // scoring and the M-step dyad statistics: upper-triangle tiles
+        ame_tri_tile_origin(tile, n, I0, J0);
         ilim = jlim = n;
     } else {
         const int ti = tile / p.ntj, tj = tile - ti * p.ntj;
-        I0 = p.i0 + ti * AME_PT;
-        J0 = p.j0 + tj * AME_PT;
+        I0 = p.i0 + ti * AME_DT;
+        J0 = p.j0 + tj * AME_DT;
         ilim = p.i1;
         jlim = p.j1;
     }
-    if (MODE == 2) {   // M-step dyad statistics: MODE 0's upper-triangle tiles
-        const int nb = (n + AME_PT - 1) / AME_PT;
-        int I = 0, rem = tile;
-        while (rem >= nb - I) { rem -= nb - I; ++I; }
-        I0 = I * AME_PT;
-        J0 = (I + rem) * AME_PT;
-        ilim = jlim = n;
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int li = lane & 15, lq = lane >> 4;
+    const AmeLaneDyad ld(I0, J0);
 
-    __shared__ __attribute__((aligned(16))) float Il[AME_PT * AME_PLD], Jl[AME_PT * AME_PLD];
+    __shared__ __attribute__((aligned(16))) float Il[AME_DT * AME_PLD], Jl[AME_DT * AME_PLD];
     __shared__ double red[4 * AME_PNS];
 
     const float* fs = p.feat + (size_t)tl * n * L;
@@ -255,8 +230,8 @@ ame_predict_pairs_kernel(PredictParams p) {
             if (c + 1 < nch) gload(c + 1);
             const int left = (len - c * AME_PKB) >> 2;
             const int ks = left < AME_PKB / 4 ? left : AME_PKB / 4;
-            const float* ia = &Il[(16 * w + li) * AME_PLD + lq];
-            const float* jb = &Jl[li * AME_PLD + lq];
+            const float* ia = &Il[ld.i_op(AME_PLD)];
+            const float* jb = &Jl[ld.j_op(0, AME_PLD)];
 #pragma unroll 2
             for (int kk = 0; kk < ks; ++kk) {
                 const float a = ia[4 * kk];
@@ -274,7 +249,7 @@ ame_predict_pairs_kernel(PredictParams p) {
     product(std::integral_constant<int, 3>{}, C::oG, C::oF, C::KVP);
     product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
 
-    // accumulator element (s, g) of this lane: i = I0 + 16 w + 4 lq + g, j = J0 + 16 s + li
+    // accumulator element (s, g) of this lane: dyad (ld.i(g), ld.j(s))
     if (MODE == 2) {   // pairs, e0^2 + V0(i,j), e1^2 + V0(j,i), e0 e1 + C01 (no noise), fp64
         double sm[AME_MS_DYAD];
 #pragma unroll
@@ -282,11 +257,11 @@ ame_predict_pairs_kernel(PredictParams p) {
         const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const int j = J0 + 16 * s + li;
+            const int j = ld.j(s);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int i = I0 + 16 * w + 4 * lq + g;
-                if (i < n && j < n && i < j && predict_pair_selected(p, tl, i, j)) {
+                const int i = ld.i(g);
+                if (ame_upper_pair(i, j, n) && predict_pair_selected(p, tl, i, j)) {
                     const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
                     const double e0 = (double)y.x - (double)acc[0][s][g];
                     const double e1 = (double)y.y - (double)acc[1][s][g];
@@ -313,11 +288,11 @@ ame_predict_pairs_kernel(PredictParams p) {
         constexpr double LOG2PI2 = 2.0 * 1.8378770664093454835606594728112;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const int j = J0 + 16 * s + li;
+            const int j = ld.j(s);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int i = I0 + 16 * w + 4 * lq + g;
-                if (i < n && j < n && i < j && predict_pair_selected(p, tl, i, j)) {
+                const int i = ld.i(g);
+                if (ame_upper_pair(i, j, n) && predict_pair_selected(p, tl, i, j)) {
                     const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
                     const double e0 = (double)y.x - (double)acc[0][s][g];
                     const double e1 = (double)y.y - (double)acc[1][s][g];
@@ -359,10 +334,10 @@ ame_predict_pairs_kernel(PredictParams p) {
         const float qnan = __builtin_nanf("");
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const int j = J0 + 16 * s + li;
+            const int j = ld.j(s);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int i = I0 + 16 * w + 4 * lq + g;
+                const int i = ld.i(g);
                 if (i < ilim && j < jlim) {
                     float* o = p.dense + (((size_t)tl * ni + (i - p.i0)) * nj + (j - p.j0)) * 5;
                     const bool dg = i == j;
@@ -377,67 +352,25 @@ ame_predict_pairs_kernel(PredictParams p) {
     }
 }
 
-// K3: one workgroup per slice sums its tiles' partials in a fixed order
-static __global__ void __launch_bounds__(AME_NT)
-ame_predict_final_kernel(const double* __restrict__ partial, int ntile, double* __restrict__ sums) {
-    __shared__ double red[4 * AME_PNS];
-    const double* ps = partial + (size_t)blockIdx.x * ntile * AME_PNS;
-    double v[AME_PNS];
-#pragma unroll
-    for (int q = 0; q < AME_PNS; ++q) v[q] = 0.0;
-    for (int b = threadIdx.x; b < ntile; b += AME_NT) {
-#pragma unroll
-        for (int q = 0; q < AME_PNS; ++q) v[q] += ps[(size_t)b * AME_PNS + q];
-    }
-    block_sum<AME_PNS>(v, red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < AME_PNS; ++q) sums[(size_t)blockIdx.x * AME_PNS + q] = v[q];
-    }
-}
-
-// K3 of the M-step dyad statistics: a slice's tile partials in tile order
-static __global__ void __launch_bounds__(AME_NT)
-ame_mstep_dyad_final_kernel(const double* __restrict__ partial, int ntile, double* __restrict__ dyad) {
-    __shared__ double red[4 * AME_MS_DYAD];
-    const double* ps = partial + (size_t)blockIdx.x * ntile * AME_MS_DYAD;
-    double v[AME_MS_DYAD];
-#pragma unroll
-    for (int q = 0; q < AME_MS_DYAD; ++q) v[q] = 0.0;
-    for (int b = threadIdx.x; b < ntile; b += AME_NT) {
-#pragma unroll
-        for (int q = 0; q < AME_MS_DYAD; ++q) v[q] += ps[(size_t)b * AME_MS_DYAD + q];
-    }
-    block_sum<AME_MS_DYAD>(v, red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < AME_MS_DYAD; ++q) dyad[(size_t)blockIdx.x * AME_MS_DYAD + q] = v[q];
-    }
-}
-
-static inline long long predict_tri_tiles(int n) {
-    const long long nb = (n + AME_PT - 1) / AME_PT;
-    return nb * (nb + 1) / 2;
-}
 static inline long long predict_feat_doubles(const ame_dims* dm) {
     return ((long long)dm->T_local * dm->n * ame_predict_row(dm->r) + 1) / 2;
 }
 
 #if AME_PART0
 long long ame_predict_work_doubles(const ame_dims* dm) {
-    return predict_feat_doubles(dm) + (long long)dm->T_local * predict_tri_tiles(dm->n) * AME_PNS;
+    return predict_feat_doubles(dm) + (long long)dm->T_local * ame_tri_tiles(dm->n) * AME_PNS;
 }
 
 // workgroups of the largest launch ame_predict would make (the caller checks it fits a grid)
 long long ame_predict_max_blocks(const ame_dims* dm, const ame_predict_args* a) {
     long long m = (long long)dm->T_local * dm->n;
     if (a->sums) {
-        const long long b = (long long)dm->T_local * predict_tri_tiles(dm->n);
+        const long long b = (long long)dm->T_local * ame_tri_tiles(dm->n);
         m = b > m ? b : m;
     }
     if (a->dense) {
-        const long long b = (long long)dm->T_local * ((a->i1 - a->i0 + AME_PT - 1) / AME_PT) *
-                            ((a->j1 - a->j0 + AME_PT - 1) / AME_PT);
+        const long long b = (long long)dm->T_local * ((a->i1 - a->i0 + AME_DT - 1) / AME_DT) *
+                            ((a->j1 - a->j0 + AME_DT - 1) / AME_DT);
         m = b > m ? b : m;
     }
     return m;
@@ -445,52 +378,66 @@ long long ame_predict_max_blocks(const ame_dims* dm, const ame_predict_args* a) 
 
 // the dyad part of ame_mstep_stats' work buffer: feature rows, then tile partials
 long long ame_mstep_dyad_work_doubles(const ame_dims* dm) {
-    return predict_feat_doubles(dm) + (long long)dm->T_local * predict_tri_tiles(dm->n) * AME_MS_DYAD;
+    return predict_feat_doubles(dm) + (long long)dm->T_local * ame_tri_tiles(dm->n) * AME_MS_DYAD;
 }
 long long ame_mstep_dyad_blocks(const ame_dims* dm) {
-    const long long a = (long long)dm->T_local * dm->n, b = (long long)dm->T_local * predict_tri_tiles(dm->n);
+    const long long a = (long long)dm->T_local * dm->n, b = (long long)dm->T_local * ame_tri_tiles(dm->n);
     return a > b ? a : b;
 }
 #endif
 
+// What ame_predict and the M-step dyad statistics share: the feature kernel into
+// the head of `work`, and the pair kernel's parameters for the upper-triangle
+// tiles, with no noise, no levels and no dense block
 template <int R>
-static int launch_predict(const ame_dims* dm, const ame_predict_args* a, hipStream_t st) {
+static PredictParams predict_common(const ame_dims* dm, const float* x, const float* cov, const float* Yt,
+                                    const void* Mt, int mask_select, double* work, hipStream_t st) {
     const int S = dm->T_local, n = dm->n;
-    float* feat = (float*)a->work;
+    float* feat = (float*)work;
     hipLaunchKernelGGL(ame_predict_feat_kernel<R>, dim3((unsigned)((long long)S * n)), dim3(AME_NT), 0, st,
-                       a->x, a->cov, feat);
+                       x, cov, feat);
     PredictParams p;
     p.n = n;
     p.S = S;
     p.ny = ame_ystride(n);
-    p.n_levels = a->n_levels;
+    p.ntile = (int)ame_tri_tiles(n);
+    p.n_levels = 0;
     p.i0 = p.i1 = p.j0 = p.j1 = 0;
     p.ntj = 1;
     p.feat = feat;
-    p.Yt = a->Yt;
+    p.Yt = Yt;
+    p.n00 = p.n01 = p.n11 = 0.0;
+    for (int l = 0; l < AME_PREDICT_MAX_LEVELS; ++l) p.zsq[l] = p.csq[l] = 0.0;
+    p.partial = work + predict_feat_doubles(dm);
+    p.dense = nullptr;
+    p.Mt = (const unsigned long long*)Mt;
+    p.nw = ame_mask_row_words(n);
+    p.mask_select = mask_select;
+    return p;
+}
+
+template <int R>
+static int launch_predict(const ame_dims* dm, const ame_predict_args* a, hipStream_t st) {
+    const int S = dm->T_local;
+    PredictParams p = predict_common<R>(dm, a->x, a->cov, a->Yt, a->Mt, a->mask_select, a->work, st);
+    p.n_levels = a->n_levels;
     p.n00 = a->noise[0];
     p.n01 = 0.5 * (a->noise[1] + a->noise[2]);
     p.n11 = a->noise[3];
-    for (int l = 0; l < AME_PREDICT_MAX_LEVELS; ++l) {
-        p.zsq[l] = l < a->n_levels ? a->zsq[l] : 0.0;
-        p.csq[l] = l < a->n_levels ? a->csq[l] : 0.0;
+    for (int l = 0; l < a->n_levels; ++l) {
+        p.zsq[l] = a->zsq[l];
+        p.csq[l] = a->csq[l];
     }
-    p.partial = a->work + predict_feat_doubles(dm);
-    p.dense = nullptr;
-    p.Mt = (const unsigned long long*)a->Mt;
-    p.nw = (n + 63) / 64;
-    p.mask_select = a->mask_select;
     if (a->sums) {
-        p.ntile = (int)predict_tri_tiles(n);
         hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 0>), dim3((unsigned)((long long)S * p.ntile)),
                            dim3(AME_NT), 0, st, p);
-        hipLaunchKernelGGL(ame_predict_final_kernel, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
+        hipLaunchKernelGGL(ame_tile_sum_kernel<AME_PNS>, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
                            p.ntile, a->sums);
     }
     if (a->dense) {
         p.i0 = a->i0; p.i1 = a->i1; p.j0 = a->j0; p.j1 = a->j1;
-        const int nti = (a->i1 - a->i0 + AME_PT - 1) / AME_PT;
-        p.ntj = (a->j1 - a->j0 + AME_PT - 1) / AME_PT;
+        const int nti = (a->i1 - a->i0 + AME_DT - 1) / AME_DT;
+        p.ntj = (a->j1 - a->j0 + AME_DT - 1) / AME_DT;
         p.ntile = nti * p.ntj;
         p.dense = a->dense;
         hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 1>), dim3((unsigned)((long long)S * p.ntile)),
@@ -503,30 +450,11 @@ static int launch_predict(const ame_dims* dm, const ame_predict_args* a, hipStre
 // M-step epilogue; `work` is the dyad part of ame_mstep_args.work
 template <int R>
 static int launch_mstep_dyad(const ame_dims* dm, const ame_mstep_args* a, double* work, hipStream_t st) {
-    const int S = dm->T_local, n = dm->n;
-    float* feat = (float*)work;
-    hipLaunchKernelGGL(ame_predict_feat_kernel<R>, dim3((unsigned)((long long)S * n)), dim3(AME_NT), 0, st,
-                       a->x, a->cov, feat);
-    PredictParams p;
-    p.n = n;
-    p.S = S;
-    p.ny = ame_ystride(n);
-    p.n_levels = 0;
-    p.i0 = p.i1 = p.j0 = p.j1 = 0;
-    p.ntj = 1;
-    p.feat = feat;
-    p.Yt = a->Yt;
-    p.n00 = p.n01 = p.n11 = 0.0;
-    for (int l = 0; l < AME_PREDICT_MAX_LEVELS; ++l) p.zsq[l] = p.csq[l] = 0.0;
-    p.partial = work + predict_feat_doubles(dm);
-    p.dense = nullptr;
-    p.Mt = (const unsigned long long*)a->Mt;
-    p.nw = (n + 63) / 64;
-    p.mask_select = a->mask_select;
-    p.ntile = (int)predict_tri_tiles(n);
+    const int S = dm->T_local;
+    const PredictParams p = predict_common<R>(dm, a->x, a->cov, a->Yt, a->Mt, a->mask_select, work, st);
     hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 2>), dim3((unsigned)((long long)S * p.ntile)),
                        dim3(AME_NT), 0, st, p);
-    hipLaunchKernelGGL(ame_mstep_dyad_final_kernel, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
+    hipLaunchKernelGGL(ame_tile_sum_kernel<AME_MS_DYAD>, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
                        p.ntile, a->dyad);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

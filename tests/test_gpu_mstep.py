@@ -41,8 +41,11 @@ pytestmark = pytest.mark.gpu
 
 # (63, 3, 20): a 31-node chunk (the one-node-ahead prefetch stops one short of a
 # full chunk), a single tile of 63, the K = 10 state instance, a middle slice
+# (70, 8, 3): 8 slices, so the single call takes the pair kernel's XCD-aware
+# slice mapping and test_bit_identity's split calls (1..7 slices) the plain one;
+# two tile rows, an edge tile 6 wide
 SHAPES = ((5, 1, 1), (33, 3, 2), (64, 2, 3), (65, 4, 5), (130, 3, 16), (70, 2, 32), (200, 5, 8),
-          (63, 3, 20))
+          (63, 3, 20), (70, 8, 3))
 # every other compiled r at predictive_ref.GPU_SHAPES_EVERY_R's shape: two tile
 # rows with a one-wide edge tile, chunks of 32, 32 and 1 nodes, one slice without
 # a previous slice and one with.  ame_predict_pairs_kernel<R, 2> is one instance
