@@ -438,6 +438,23 @@ long long ame_mstep_work_size(const ame_dims* dims);
  * order on one stream) give the same bits as one call over all nodes.
  * No atomics in the sums and no waits between workgroups.
  *
+ * Observed partners only (missing dyads).  With `Mt` set (the words of
+ * ame_pack_mask, bit j of row i = pair {i, j} hidden) the sums of P_obs and
+ * h_obs run over obs(i,t) = { j != i : bit j of row i of slice t clear }:
+ *   P_obs^m(i,t) = sum_{j in obs(i,t)} J_j' sym(R_inv) J_j
+ *   h_t          = sum_{j in obs(i,t)} J_j' R_inv y_ij
+ * the exact posterior of node i's trajectory given the other nodes' means and
+ * only the dyads it has observed.  `Yt` is then the RAW packed network (never the
+ * working network of ame_fill_missing): hidden entries are not read into h.
+ * The observation stage gains one kernel: per (node, slice) the Gram matrix
+ * H = sum_{j hidden} w_j w_j', w = [1, U_j, V_j], gathered in ascending j in
+ * chunks of four partners on fp64 MFMA (fp32 rows widened, products exact), one
+ * wave per (node, slice), into `work`; the solve stage assembles
+ * sym(R_inv) (.) ((G - w_i w_i') - H).  A node with every partner hidden in a
+ * slice keeps the prior blocks only.  An all-zero mask gives the bits of the
+ * Mt = NULL call; the bits do not depend on how the nodes are split over calls.
+ * `work` then needs ame_smooth_masked_work_size doubles.
+ *
  * Failure: a non-positive (or NaN) pivot does not fault; that node's outputs
  * (and lag_sum) become NaN and `fail` records it: [0] nodes that failed, [1]
  * claim word, [2] node and [3] slice of the first to report.  The caller zeroes
@@ -461,12 +478,18 @@ typedef struct ame_smooth_args {
     uint32_t* fail;          /* [AME_SMOOTH_FAIL_WORDS] */
     double* work;            /* >= ame_smooth_work_size(dims, i1 - i0) doubles */
     uint64_t work_doubles;   /* size of `work` in doubles, checked */
+    const uint64_t* Mt;      /* [T][n][nw] hidden-pair words (ame_pack_mask) or NULL: sums over
+                                the observed partners only; Yt is then the raw network and
+                                work holds >= ame_smooth_masked_work_size doubles */
 } ame_smooth_args;
 int ame_smooth(const ame_dims* dims, const ame_smooth_args* args, void* stream);
 /* Scratch doubles one ame_smooth call over `nodes` nodes needs: T (1+2r)^2 Gram
  * statistics + nodes T (d^2 + 2d) (h_obs, J_t^-1 g_t, J_t^-1); -1 on bad
  * dims or nodes outside [1, n]. */
 long long ame_smooth_work_size(const ame_dims* dims, int nodes);
+/* The same with `Mt` set: ame_smooth_work_size + nodes T (1+2r)^2 (the hidden
+ * partners' Gram matrices); -1 in the same cases. */
+long long ame_smooth_masked_work_size(const ame_dims* dims, int nodes);
 /* Dynamic LDS bytes of the solve workgroup at latent dim r (four d x (d+1) fp64
  * matrices and six d-vectors), -1 for an r that is not compiled in. */
 long long ame_smooth_lds_bytes(int r);

@@ -91,7 +91,7 @@ class ame_smooth_args(ctypes.Structure):
     _fields_ = [("x", c_vp), ("Yt", c_vp), ("consts", c_vp), ("rinv", ctypes.c_double * 4),
                 ("i0", c_int32), ("i1", c_int32), ("stages", c_int32), ("mean", c_vp), ("cov", c_vp),
                 ("cross", c_vp), ("lag_sum", c_vp), ("fail", c_vp), ("work", c_vp),
-                ("work_doubles", ctypes.c_uint64)]
+                ("work_doubles", ctypes.c_uint64), ("Mt", c_vp)]
 
 
 AME_MAX_COVARIATES = 8
@@ -113,7 +113,7 @@ class ame_fill_args(ctypes.Structure):
 
 # every symbol include/ame_amd.h declares (checked by tests/test_capi.py)
 EXPORTS = ("ame_pack_y", "ame_pack_y_size", "ame_sweep", "ame_sweep_kind", "ame_sweep_work_size", "ame_sweep_orders_slices", "ame_sweep_max_slices", "ame_sweep_slice_workgroups", "ame_sweep_lds_bytes", "ame_cov",
-           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_smooth", "ame_smooth_work_size", "ame_smooth_lds_bytes", "ame_covar_stats", "ame_covar_work_size", "ame_covar_resid", "ame_mask_words", "ame_pack_mask", "ame_fill_missing", "ame_fill_work_size", "ame_host_register", "ame_host_unregister",
+           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_smooth", "ame_smooth_work_size", "ame_smooth_masked_work_size", "ame_smooth_lds_bytes", "ame_covar_stats", "ame_covar_work_size", "ame_covar_resid", "ame_mask_words", "ame_pack_mask", "ame_fill_missing", "ame_fill_work_size", "ame_host_register", "ame_host_unregister",
            "ame_stream_create_cu_range", "ame_stream_destroy",
            "ame_peer_alloc", "ame_peer_free", "ame_peer_open", "ame_peer_close",
            "ame_peer_probe", "ame_peer_read_u64", "ame_peer_clear",
@@ -153,6 +153,8 @@ def _declare(L):
     L.ame_smooth.restype = ctypes.c_int
     L.ame_smooth_work_size.argtypes = [P(ame_dims), ctypes.c_int]
     L.ame_smooth_work_size.restype = ctypes.c_longlong
+    L.ame_smooth_masked_work_size.argtypes = [P(ame_dims), ctypes.c_int]
+    L.ame_smooth_masked_work_size.restype = ctypes.c_longlong
     L.ame_smooth_lds_bytes.argtypes = [ctypes.c_int]
     L.ame_smooth_lds_bytes.restype = ctypes.c_longlong
     L.ame_covar_stats.argtypes = [P(ame_dims), P(ame_covar_args), c_vp]

@@ -33,6 +33,7 @@ long long ame_mstep_dyad_work_doubles(const ame_dims*);
 long long ame_mstep_dyad_blocks(const ame_dims*);
 int ame_smooth_dispatch(const ame_dims*, const ame_smooth_args*, hipStream_t);
 long long ame_smooth_work_doubles(const ame_dims*, int nodes);
+long long ame_smooth_hidden_doubles(const ame_dims*, int nodes);
 long long ame_smooth_lds_bytes_r(int r);
 int ame_covar_stats_dispatch(const ame_dims*, const ame_covar_args*, hipStream_t);
 int ame_covar_resid_dispatch(const ame_dims*, const float* Yraw, const float* Wt, const double* beta, int p,
@@ -600,6 +601,13 @@ long long ame_smooth_work_size(const ame_dims* dims, int nodes) {
     return ame_smooth_work_doubles(dims, nodes);
 }
 
+long long ame_smooth_masked_work_size(const ame_dims* dims, int nodes) {
+    if (check_dims(dims)) return -1;
+    if (nodes < 1 || nodes > dims->n)
+        return fail("ame_smooth_masked_work_size: nodes=%d outside [1, n]", nodes);
+    return ame_smooth_work_doubles(dims, nodes) + ame_smooth_hidden_doubles(dims, nodes);
+}
+
 long long ame_smooth_lds_bytes(int r) {
     if (!r_supported(r)) return fail("ame_smooth_lds_bytes: latent_dim r=%d not compiled into this library", r);
     return ame_smooth_lds_bytes_r(r);
@@ -624,6 +632,15 @@ int ame_smooth(const ame_dims* dims, const ame_smooth_args* a, void* stream) {
     if ((long long)a->work_doubles < need)
         return fail("ame_smooth: work holds fewer doubles than ame_smooth_work_size (%d nodes)",
                     a->i1 - a->i0);
+    if (a->Mt) {
+        if ((uintptr_t)a->Mt & 7) return fail("ame_smooth: Mt must be 8-byte aligned");
+        if ((long long)a->work_doubles < need + ame_smooth_hidden_doubles(dims, a->i1 - a->i0))
+            return fail("ame_smooth: with Mt set, work holds fewer doubles than "
+                        "ame_smooth_masked_work_size (%d nodes)", a->i1 - a->i0);
+        if (((long long)dims->T_local * (a->i1 - a->i0) + 3) / 4 > 0x7FFFFFFFLL)
+            return fail("ame_smooth: T_local=%d slices of %d nodes exceed one launch; pass fewer nodes",
+                        dims->T_local, a->i1 - a->i0);
+    }
     if ((long long)dims->T_local * ((a->i1 - a->i0 + 31) / 32) > 0x7FFFFFFFLL)
         return fail("ame_smooth: T_local=%d slices of %d nodes exceed one launch; pass fewer nodes",
                     dims->T_local, a->i1 - a->i0);

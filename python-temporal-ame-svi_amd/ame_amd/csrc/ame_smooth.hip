@@ -20,6 +20,19 @@
 //  K2 ame_smooth_h_kernel: h_obs for 32 nodes x one slice per workgroup; the row
 //     of Y is read once, z_ij = R_inv y_ij in fp64 (zero at j = i), and the (U, V)
 //     block streams through LDS in tiles of 64 nodes, so it never has to fit.
+//  K2m ame_smooth_hgram_kernel (with a mask only): one wave per (slice, node),
+//     four per workgroup.  The wave walks the set bits of the node's mask words
+//     in ascending j, four partners to a chunk, and adds one step of
+//     v_mfma_f64_16x16x4_f64 per lower-triangle tile of the 2r x 2r (U, V) Gram
+//     matrix (operands and lane mapping of p0_gram_mfma, ame_sweep_dev.h: lane l
+//     holds partner l >> 4 of the chunk, column 16 I + (l & 15); rows gathered
+//     from x in fp32 and widened, so the products are exact; lanes of an
+//     incomplete last chunk and columns >= 2r hold zero).  Column sums come
+//     from the same registers by a fixed shuffle tree, the count is the
+//     popcount.  H(i,t) = sum_{j hidden} w_j w_j' goes to `work` in G's index
+//     order, both triangles, and P_obs over the observed partners is
+//     sym(R_inv) (.) ((G - w_i w_i') - H).  K2 then takes z_ij = 0 at a hidden j.
+//     The order of the sum is a property of the (slice, node) alone.
 // Solve stage
 //  K3 ame_smooth_solve_kernel: one workgroup per node, sequential in t.
 //     Forward:  J_t = D_t - QiPhi J_{t-1}^-1 QiPhi',  g_t = h_t + QiPhi J_{t-1}^-1 g_{t-1};
@@ -34,10 +47,11 @@
 //  K4 ame_smooth_lag_kernel: lag_sum[t] += chunk partials of the fp64 X_t in
 //     fixed chunks of 32 nodes, chunk by chunk in node order.
 // No atomics in any sum, no waits between workgroups.
-#include "ame_common.h"
+#include "ame_tile.h"   // ame_mask_row_words: the row layout of ame_pack_mask
 
-#define AME_SM_CHUNK 32     // nodes per lag_sum partial, rows per h workgroup
+#define AME_SM_CHUNK 32    // nodes per lag_sum partial, rows per h workgroup
 #define AME_SM_JT 64        // nodes per (U, V) tile of the h kernel
+#define AME_SM_HW 4         // waves, one (slice, node) each, per hidden-Gram workgroup
 #define AME_SM_MAXD (2 + 2 * AME_MAX_R)
 
 __host__ __device__ inline long long ame_smooth_lds(int r) {
@@ -87,7 +101,7 @@ ame_smooth_gram_kernel(const float* __restrict__ x, int n, int r, double* __rest
 __global__ void __launch_bounds__(AME_NT)
 ame_smooth_h_kernel(const float* __restrict__ Yt, const float* __restrict__ x, int n, int ny, int r,
                     int T, int i0, int nc, double r00, double r01, double r10, double r11,
-                    double* __restrict__ hbuf) {
+                    double* __restrict__ hbuf, const unsigned long long* __restrict__ Mt, int nw) {
     __shared__ double z[AME_SM_CHUNK][2 * AME_SM_JT + 2];
     __shared__ float wt[AME_SM_JT][AME_SM_MAXD + 1];
     const int d = 2 + 2 * r, tid = threadIdx.x;
@@ -115,7 +129,10 @@ ame_smooth_h_kernel(const float* __restrict__ Yt, const float* __restrict__ x, i
         for (int e = tid; e < AME_SM_CHUNK * AME_SM_JT; e += AME_NT) {
             const int rr = e / AME_SM_JT, jj = e - rr * AME_SM_JT, i = ib + rr, j = j0 + jj;
             double z0 = 0.0, z1 = 0.0;
-            if (i < iend && j < n && j != i) {
+            bool on = i < iend && j < n && j != i;
+            // rr is the same for the 64 lanes of a wave and j0 a multiple of 64: one word per wave
+            if (Mt && on) on = !((Mt[((size_t)t * n + i) * nw + (j0 >> 6)] >> jj) & 1ull);
+            if (on) {
                 const float2 y = *reinterpret_cast<const float2*>(Yt + (((size_t)t * n + i) * ny + j) * 2);
                 z0 = r00 * (double)y.x + r01 * (double)y.y;
                 z1 = r10 * (double)y.x + r11 * (double)y.y;
@@ -143,6 +160,109 @@ ame_smooth_h_kernel(const float* __restrict__ Yt, const float* __restrict__ x, i
             if (c < d) o[c] = acc[q];
         }
     }
+}
+
+// ---- K2m: Gram matrix of the hidden partners of one (slice, node) per wave ----
+typedef double ame_smd4 __attribute__((ext_vector_type(4)));
+template <int NT>
+__global__ void __launch_bounds__(64 * AME_SM_HW)
+ame_smooth_hgram_kernel(const float* __restrict__ x, const unsigned long long* __restrict__ Mt, int n,
+                        int nw, int r, int T, int i0, int nc, double* __restrict__ H) {
+    constexpr int NTL = NT * (NT + 1) / 2;
+    const int lane = threadIdx.x & 63;
+    // the wave's index as a scalar: the walk over the mask words below is wave-uniform
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long g = (long long)blockIdx.x * AME_SM_HW + wv;
+    if (g >= (long long)T * nc) return;   // a whole wave; the kernel has no barrier
+    const int t = (int)(g / nc), ii = (int)(g - (long long)t * nc), node = i0 + ii;
+    const int d = 2 + 2 * r, M2 = 2 * r, W = 1 + 2 * r;
+    const int ci = lane & 15, ck = lane >> 4;
+    ame_smd4 acc[NTL];
+#pragma unroll
+    for (int q = 0; q < NTL; ++q) acc[q] = ame_smd4{0.0, 0.0, 0.0, 0.0};
+    double cs[NT];
+#pragma unroll
+    for (int I = 0; I < NT; ++I) cs[I] = 0.0;
+    const float* xs = x + (size_t)t * n * d;
+    const unsigned long long* row = Mt + ((size_t)t * n + node) * nw;
+
+    // one chunk: lane (ck, ci) holds partner p[ck]'s columns 16 I + ci, zero past `cnt` partners
+    auto chunk = [&](int p0, int p1, int p2, int p3, int cnt) {
+        const int j = ck == 0 ? p0 : ck == 1 ? p1 : ck == 2 ? p2 : p3;
+        const bool ok = ck < cnt;
+        double xd[NT];
+#pragma unroll
+        for (int I = 0; I < NT; ++I) {
+            const int col = 16 * I + ci;
+            xd[I] = (double)((ok && col < M2) ? xs[(size_t)j * d + 2 + col] : 0.f);
+            cs[I] += xd[I];
+        }
+#pragma unroll
+        for (int I = 0; I < NT; ++I)
+#pragma unroll
+            for (int J = 0; J <= I; ++J) {
+                const int q = I * (I + 1) / 2 + J;
+                acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(xd[I], xd[J], acc[q], 0, 0, 0);
+            }
+    };
+
+    int p0 = 0, p1 = 0, p2 = 0, cnt = 0, total = 0;   // wave-uniform
+    for (int w = 0; w < nw; ++w) {
+        const unsigned long long raw = row[w];
+        // (the builtin returns a signed int: widen each half as unsigned)
+        const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)raw);
+        const unsigned int hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(raw >> 32));
+        unsigned long long word = ((unsigned long long)hi << 32) | (unsigned long long)lo;
+        // partners are j < n, j != node whatever the words hold
+        const int left = n - 64 * w;
+        if (left < 64) word &= (1ull << left) - 1ull;
+        if ((node >> 6) == w) word &= ~(1ull << (node & 63));
+        total += __builtin_popcountll(word);
+        while (word) {
+            const int j = 64 * w + __builtin_ctzll(word);
+            word &= word - 1ull;
+            if (cnt == 0) p0 = j;
+            else if (cnt == 1) p1 = j;
+            else if (cnt == 2) p2 = j;
+            if (++cnt == 4) {
+                chunk(p0, p1, p2, j, 4);
+                cnt = 0;
+            }
+        }
+    }
+    if (cnt) chunk(p0, p1, p2, 0, cnt);
+
+    // column sums: the 4 partner lanes of a column, fixed tree
+#pragma unroll
+    for (int I = 0; I < NT; ++I) {
+        const double s1 = cs[I] + __shfl_xor(cs[I], 16);
+        cs[I] = s1 + __shfl_xor(s1, 32);
+    }
+    double* Hn = H + ((size_t)ii * T + t) * W * W;
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = 0; J <= I; ++J) {
+            const int q = I * (I + 1) / 2 + J;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int a = 16 * I + ck + 4 * v, b = 16 * J + ci;
+                if (a >= M2 || b >= M2) continue;
+                Hn[(1 + a) * W + 1 + b] = acc[q][v];
+                if (I != J) Hn[(1 + b) * W + 1 + a] = acc[q][v];
+            }
+        }
+    if (ck == 0) {
+#pragma unroll
+        for (int I = 0; I < NT; ++I) {
+            const int a = 16 * I + ci;
+            if (a < M2) {
+                Hn[1 + a] = cs[I];
+                Hn[(1 + a) * W] = cs[I];
+            }
+        }
+    }
+    if (lane == 0) Hn[0] = (double)total;
 }
 
 // ---- K3 helpers ----
@@ -202,7 +322,7 @@ ame_smooth_solve_kernel(const float* __restrict__ x, const double* __restrict__ 
                         const double* __restrict__ G, const double* __restrict__ hbuf,
                         double* mfbuf, double* fac, int n, int r, int T, int i0, double rs00,
                         double rs01, double rs11, float* __restrict__ mean, float* __restrict__ cov,
-                        float* __restrict__ cross, uint32_t* fail) {
+                        float* __restrict__ cross, uint32_t* fail, const double* __restrict__ Hb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_bad[2];
     const int d = 2 + 2 * r, DS = d + 1, W = 1 + 2 * r, dd = d * d, tid = threadIdx.x;
@@ -221,6 +341,7 @@ ame_smooth_solve_kernel(const float* __restrict__ x, const double* __restrict__ 
     double* facn = fac + (size_t)ii * T * dd;
     double* mfn = mfbuf + (size_t)ii * T * d;
     const double* hn = hbuf + (size_t)ii * T * d;
+    const double* Hn = Hb ? Hb + (size_t)ii * T * W * W : nullptr;   // hidden partners' Gram, or no mask
     const int tx = tid & 15, ty = tid >> 4;
 
     if (tid == 0) {
@@ -246,7 +367,9 @@ ame_smooth_solve_kernel(const float* __restrict__ x, const double* __restrict__ 
             sm_index(k, r, sk, wk);
             sm_index(m, r, sm, wm);
             const double rsv = (sk == sm) ? (sk ? rs11 : rs00) : rs01;
-            M1[k * DS + m] = pconst_entry(consts, d, k, m, t, T) + rsv * (Gt[wk * W + wm] - wi[wk] * wi[wm]);
+            double gv = Gt[wk * W + wm] - wi[wk] * wi[wm];
+            if (Hn) gv -= Hn[(size_t)t * W * W + wk * W + wm];
+            M1[k * DS + m] = pconst_entry(consts, d, k, m, t, T) + rsv * gv;
         }
         __syncthreads();
         if (t > 0) {
@@ -427,6 +550,12 @@ long long ame_smooth_work_doubles(const ame_dims* dm, int nodes) {
     return T * W * W + (long long)nodes * T * (2 * d + d * d);
 }
 
+// with a mask, appended: H [nc][T][W][W]
+long long ame_smooth_hidden_doubles(const ame_dims* dm, int nodes) {
+    const long long W = 1 + 2 * dm->r;
+    return (long long)nodes * dm->T_local * W * W;
+}
+
 long long ame_smooth_lds_bytes_r(int r) { return ame_smooth_lds(r); }
 
 int ame_smooth_dispatch(const ame_dims* dm, const ame_smooth_args* a, hipStream_t st) {
@@ -436,6 +565,9 @@ int ame_smooth_dispatch(const ame_dims* dm, const ame_smooth_args* a, hipStream_
     double* hbuf = G + (size_t)T * W * W;
     double* mfbuf = hbuf + (size_t)nc * T * d;
     double* fac = mfbuf + (size_t)nc * T * d;
+    double* Hb = a->Mt ? fac + (size_t)nc * T * dd : nullptr;
+    const unsigned long long* Mt = (const unsigned long long*)a->Mt;
+    const int nw = ame_mask_row_words(n);
     const int stages = a->stages ? a->stages : (AME_SMOOTH_STAGE_OBS | AME_SMOOTH_STAGE_SOLVE);
     if (stages & AME_SMOOTH_STAGE_OBS) {
         const int K = (W * W + AME_NT - 1) / AME_NT;
@@ -451,7 +583,21 @@ int ame_smooth_dispatch(const ame_dims* dm, const ame_smooth_args* a, hipStream_
         const int nrb = (nc + AME_SM_CHUNK - 1) / AME_SM_CHUNK;
         hipLaunchKernelGGL(ame_smooth_h_kernel, dim3((unsigned)((long long)T * nrb)), dim3(AME_NT), 0, st,
                            a->Yt, a->x, n, ame_ystride(n), r, T, i0, nc, a->rinv[0], a->rinv[1],
-                           a->rinv[2], a->rinv[3], hbuf);
+                           a->rinv[2], a->rinv[3], hbuf, Mt, nw);
+        if (Mt) {
+            const dim3 grid((unsigned)(((long long)T * nc + AME_SM_HW - 1) / AME_SM_HW));
+#define AME_SM_HGRAM(NT) \
+    hipLaunchKernelGGL(ame_smooth_hgram_kernel<NT>, grid, dim3(64 * AME_SM_HW), 0, st, a->x, Mt, n, nw, r, \
+                       T, i0, nc, Hb)
+            switch ((2 * r + 15) / 16) {
+                case 1: AME_SM_HGRAM(1); break;
+                case 2: AME_SM_HGRAM(2); break;
+                case 3: AME_SM_HGRAM(3); break;
+                case 4: AME_SM_HGRAM(4); break;
+                default: return -1;
+            }
+#undef AME_SM_HGRAM
+        }
     }
     if (stages & AME_SMOOTH_STAGE_SOLVE) {
         const int lds = (int)ame_smooth_lds(r);
@@ -461,7 +607,7 @@ int ame_smooth_dispatch(const ame_dims* dm, const ame_smooth_args* a, hipStream_
         hipLaunchKernelGGL(ame_smooth_solve_kernel, dim3(nc), dim3(AME_NT), (size_t)lds, st, a->x,
                            a->consts, G, hbuf, mfbuf, fac, n, r, T, i0, a->rinv[0],
                            0.5 * (a->rinv[1] + a->rinv[2]), a->rinv[3], a->mean, a->cov, a->cross,
-                           a->fail);
+                           a->fail, Hb);
         const long long total = (long long)T * dd;
         hipLaunchKernelGGL(ame_smooth_lag_kernel, dim3((unsigned)((total + AME_NT - 1) / AME_NT)),
                            dim3(AME_NT), 0, st, fac, nc, T, dd, i0 == 0 ? 1 : 0, a->lag_sum);

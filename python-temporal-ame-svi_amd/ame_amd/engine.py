@@ -1066,19 +1066,21 @@ class DeviceEngine:
     # ------------------------------------------------------------------
     # exact per-node smoothing across time (ame_smooth)
     # ------------------------------------------------------------------
-    def smooth_chunk(self):
+    def smooth_chunk(self, observed=False):
         """Nodes per ame_smooth call within the scratch budget of predict(): all n,
-        or a multiple of 32 (at least 32)."""
+        or a multiple of 32 (at least 32).  ``observed``: of a call with the mask
+        (ame_smooth_masked_work_size)."""
         n = self.n
-        w1 = int(self.L.ame_smooth_work_size(ctypes.byref(self.dims), 1))
-        w2 = int(self.L.ame_smooth_work_size(ctypes.byref(self.dims), 2)) if n >= 2 else -1
+        size = self.L.ame_smooth_masked_work_size if observed else self.L.ame_smooth_work_size
+        w1 = int(size(ctypes.byref(self.dims), 1))
+        w2 = int(size(ctypes.byref(self.dims), 2)) if n >= 2 else -1
         if w1 < 0 or w2 < 0:
             _lib.check(-1, "ame_smooth_work_size")
         per, base = w2 - w1, 2 * w1 - w2
         fit = (self.PREDICT_WORK_DOUBLES - base) // per
         return n if fit >= n else min(n, max(32, fit // 32 * 32))
 
-    def smooth(self, stages=0, check=True):
+    def smooth(self, stages=0, check=True, observed=False):
         """Each node's exact Gaussian posterior across time given the current
         means of the others (include/ame_amd.h, ame_smooth): new device tensors
         ``mean`` [T][n][d], ``cov`` and ``cross`` [T][n][d][d] (fp32) and
@@ -1086,17 +1088,26 @@ class DeviceEngine:
         nothing the sweep reads.  Nodes go in chunks (multiples of 32) within
         the scratch budget of predict(); the result has the same bits for any
         chunking.  A node whose factorisation met a non-positive pivot raises
-        RuntimeError (its outputs are NaN).  Runs on the ELBO stream."""
+        RuntimeError (its outputs are NaN).  Runs on the ELBO stream.
+        With hidden dyads the call is refused unless ``observed=True``: the sums
+        then run over each node's observed partners only (Yt_raw and Mt), so the
+        covariances widen with the number of hidden partners."""
         if self.halo is not None or self.shard.T_local != self.shard.T_total:
             raise NotImplementedError("smooth is not available on a time-sharded run")
-        if self.masked:
-            raise NotImplementedError("smooth is not available with missing dyads: its observation "
-                                      "stage has no mask")
+        if observed and not self.masked:
+            raise ValueError("smooth(observed=True) needs a mask (model.set_missing)")
+        if self.masked and not observed:
+            raise NotImplementedError("smooth over all partners is not available with missing dyads: "
+                                      "its observation stage would read hidden entries; pass "
+                                      "observed=True (vi.smooth(partners=\"observed\"), "
+                                      "smoothed=\"observed\")")
         self.discard_speculation()
         n, d, T = self.n, self.d, self.shard.T_local
-        chunk = self.smooth_chunk()
-        wk = self._scratch(int(self.L.ame_smooth_work_size(ctypes.byref(self.dims), chunk)))
+        chunk = self.smooth_chunk(observed)
+        size = self.L.ame_smooth_masked_work_size if observed else self.L.ame_smooth_work_size
+        wk = self._scratch(int(size(ctypes.byref(self.dims), chunk)))
         x = self.x_a
+        Yt, Mt = (self.Yt_raw, self.Mt) if observed else (self.Yt, None)
         with torch.cuda.device(self.dev):
             mean =torch.empty(T, n, d, dtype=torch.float32, device=self.dev)
             cov = torch.empty(T, n, d, d, dtype=torch.float32, device=self.dev)
@@ -1106,14 +1117,14 @@ class DeviceEngine:
         with self._elbo_call("smooth") as sp:
             for i0 in range(0, n, chunk):
                 a = _lib.ame_smooth_args(
-                    x=_ptr(x), Yt=_ptr(self.Yt), consts=_ptr(self.consts), rinv=self.C.rinv4(),
+                    x=_ptr(x), Yt=_ptr(Yt), consts=_ptr(self.consts), rinv=self.C.rinv4(),
                     i0=i0, i1=min(n, i0 + chunk), stages=int(stages), mean=_ptr(mean), cov=_ptr(cov),
                     cross=_ptr(cross), lag_sum=_ptr(lag), fail=_ptr(fail), work=_ptr(wk),
-                    work_doubles=wk.numel())
+                    work_doubles=wk.numel(), Mt=_ptr(Mt) if Mt is not None else None)
                 _lib.check(self.L.ame_smooth(ctypes.byref(self.dims), ctypes.byref(a), sp),
                            "ame_smooth")
         st = self._elbo_stream()
-        for t in (x, self.Yt, self.consts, wk, mean, cov, cross, lag, fail):
+        for t in (x, Yt, self.consts, wk, mean, cov, cross, lag, fail) + (() if Mt is None else (Mt,)):
             t.record_stream(st)
         if check:
             words = [int(w) & 0xFFFFFFFF for w in fail.cpu().tolist()]

@@ -301,26 +301,46 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         return eng
 
     # ---------------- exact smoothing across time (extension) ----------------
-    def smooth(self) -> SmoothResult:
+    def smooth(self, partners=None) -> SmoothResult:
         """Each node's exact Gaussian posterior over its whole trajectory given
         the current means of the other nodes (ame_smooth): smoothed means, the
         time-marginal covariances (never smaller than the fit's mean-field
         blocks) and the lag-one cross-covariances.  Does not modify this object.
-        Not available on a time-sharded run."""
+        Not available on a time-sharded run.
+        With hidden dyads (model.set_missing) the default call is refused;
+        ``partners="observed"`` conditions each node on the dyads it has observed
+        only, so its covariances widen with the number of hidden partners."""
+        if partners not in (None, "observed"):
+            raise ValueError(f'partners must be None or "observed" (got {partners!r})')
         if self._time_sharded():
             raise NotImplementedError("smooth is not available on a time-sharded run: the forward "
                                       "pass would have to carry (J_t^-1, g_t) across ranks")
-        if getattr(self.model, "missing", None) is not None:
-            raise NotImplementedError("smooth() / smoothed=True are not available with missing dyads: "
-                                      "the observation stage of ame_smooth has no mask")
+        masked = getattr(self.model, "missing", None) is not None
+        if partners == "observed" and not masked:
+            raise ValueError('partners="observed" / smoothed="observed" need a mask (model.set_missing)')
+        if masked and partners is None:
+            raise NotImplementedError("smooth() / smoothed=True over all partners are not available "
+                                      "with missing dyads: use smooth(partners=\"observed\") / "
+                                      "smoothed=\"observed\"")
         eng = self._predict_engine()
-        return SmoothResult(*eng.smooth())
+        return SmoothResult(*eng.smooth(observed=partners == "observed"))
+
+    @staticmethod
+    def _partners(smoothed):
+        """The ``partners`` of :meth:`smooth` a ``smoothed`` argument asks for:
+        "observed" by name, None for any other true value."""
+        if isinstance(smoothed, str):
+            if smoothed != "observed":
+                raise ValueError(f'smoothed must be False, True or "observed" (got {smoothed!r})')
+            return "observed"
+        return None
 
     def _state(self, smoothed):
         """(engine, means, covariances, smoothing result or None) the extension
-        calls work from: the fit's state, or its smoothed counterpart."""
+        calls work from: the fit's state, or its smoothed counterpart
+        (smoothed=True, or "observed" with hidden dyads)."""
         if smoothed:
-            sm = self.smooth()
+            sm = self.smooth(partners=self._partners(smoothed))
             return self._engine, sm.d_mean, sm.d_cov, sm
         eng = self._predict_engine()
         return eng, eng.x_a, eng.cov, None
@@ -349,8 +369,10 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         (T, L, 2) and ``joint_coverage`` (T, L) as fractions, and ``levels``.
         include_noise=False scores against the credible region of the mean.
         smoothed=True scores the smoothed means and covariances (:meth:`smooth`)
-        instead of the fit's.  Time-sharded: a collective, every rank returns all
-        T steps.  With hidden dyads (model.set_missing) ``subset`` chooses the
+        instead of the fit's (with hidden dyads: smoothed="observed", the
+        smoother over each node's observed partners, whose covariances widen with
+        the number of hidden partners).  Time-sharded: a collective, every rank
+        returns all T steps.  With hidden dyads (model.set_missing) ``subset`` chooses the
         pairs: "observed" (the default) scores the pairs the fit has seen,
         "held_out" the hidden ones against ``model.Y``, out of sample; ``pairs``
         counts the chosen ones."""
@@ -419,7 +441,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
 
     def _forecast_states(self, n_steps, smoothed=False):
         if smoothed:   # the smoothed last slice is the filtered one
-            eng, x, cov, _ = self._state(True)
+            eng, x, cov, _ = self._state(smoothed)
             return eng, eng.forecast_states(x[-1], cov[-1], n_steps)
         eng = self._predict_engine()
         if self._halo is None:
@@ -497,11 +519,13 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         cross-covariances added into A10."""
         from .. import mstep
         if smoothed:
-            eng, x, cov, sm = self._state(True)
+            eng, x, cov, sm = self._state(smoothed)
             state, dyad = eng.mstep_stats(x, cov)
             stats = mstep.combine(state, dyad, cross=sm.d_lag_sum)
             if eng.p:
                 stats.update(mstep.combine_covar(*eng.covar_stats(x), eng.beta))
+            if eng.masked:
+                stats["hidden_pairs"] = float(sum(eng.hidden_pairs))
             return stats
         eng = self._predict_engine()
         state, dyad = eng.mstep_stats()
@@ -580,8 +604,12 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         the statistics)."""
         if smoothed and self._time_sharded():
             raise NotImplementedError("smoothed=True is not available on a time-sharded run")
-        if smoothed and getattr(self.model, "missing", None) is not None:
-            raise NotImplementedError("smoothed=True is not available with missing dyads")
+        masked = getattr(self.model, "missing", None) is not None
+        if smoothed and self._partners(smoothed) is None and masked:
+            raise NotImplementedError("smoothed=True is not available with missing dyads: use "
+                                      "smoothed=\"observed\"")
+        if smoothed and self._partners(smoothed) == "observed" and not masked:
+            raise ValueError('smoothed="observed" needs a mask (model.set_missing)')
         em = self.history.setdefault("em", [])
         for k in range(int(n_rounds)):
             self.fit(max_iter=inner_iter, tolerance=tolerance, verbose=False)
