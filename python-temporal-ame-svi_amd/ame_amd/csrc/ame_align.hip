@@ -17,6 +17,7 @@
 #include <stdio.h>
 
 #include "ame_common.h"
+#include "ame_internal.h"
 
 namespace {
 

@@ -4,50 +4,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "ame_internal.h"
 #include "ame_tile.h"
-
-int ame_sweep_dispatch(const ame_dims*, const ame_sweep_args*, hipStream_t);
-int ame_sweep_blocks_per_cu(int n, int r, int mode);
-int ame_sweep_workers_fit(const ame_dims* dm, int mode);   // mode 2: kind 22, 3: kind 23, 4: kind 24
-int ame_sweep3_dispatch(const ame_dims*, const ame_sweep_args*, hipStream_t);
-int ame_sweep3_supported(int n, int r);
-int ame_sweep3_blocks_per_cu(int n, int r);
-long long ame_sweep3_work_doubles(const ame_dims*);
-int ame_sweep3_lds(int n, int r);
-int ame_cov_dispatch(const ame_dims*, const ame_cov_args*, hipStream_t);
-int ame_elbo_dispatch(const ame_dims*, const ame_elbo_args*, hipStream_t, int pairs_only);
-long long ame_elbo_work_doubles(const ame_dims*);
-int ame_align_cross_dispatch(const float*, const float*, int, int, int, int, double*, double*,
-                             hipStream_t);
-int ame_align_apply_dispatch(const float*, const float*, int, int, int, int, const double*, float*,
-                             double*, hipStream_t);
-long long ame_align_partials_count(int n, int T);
-int ame_predict_dispatch(const ame_dims*, const ame_predict_args*, hipStream_t);
-long long ame_predict_work_doubles(const ame_dims*);
-long long ame_predict_max_blocks(const ame_dims*, const ame_predict_args*);
-int ame_mstep_state_dispatch(const ame_dims*, const ame_mstep_args*, hipStream_t);
-long long ame_mstep_state_work_doubles(const ame_dims*);
-long long ame_mstep_state_blocks(const ame_dims*);
-int ame_mstep_dyad_dispatch(const ame_dims*, const ame_mstep_args*, double* work, hipStream_t);
-long long ame_mstep_dyad_work_doubles(const ame_dims*);
-long long ame_mstep_dyad_blocks(const ame_dims*);
-int ame_smooth_dispatch(const ame_dims*, const ame_smooth_args*, hipStream_t);
-long long ame_smooth_work_doubles(const ame_dims*, int nodes);
-long long ame_smooth_hidden_doubles(const ame_dims*, int nodes);
-long long ame_smooth_lds_bytes_r(int r);
-int ame_covar_stats_dispatch(const ame_dims*, const ame_covar_args*, hipStream_t);
-int ame_covar_resid_dispatch(const ame_dims*, const float* Yraw, const float* Wt, const double* beta, int p,
-                             float* out, hipStream_t);
-long long ame_covar_work_doubles(const ame_dims*, int p);
-long long ame_covar_blocks(const ame_dims*);
-long long ame_covar_plane4(const ame_dims*);
-int ame_pack_dispatch(const float*, float*, const ame_dims*, unsigned long long*, hipStream_t);
-int ame_pack_mask_dispatch(const uint8_t* M, unsigned long long* Mt, const ame_dims*, unsigned long long* pairs,
-                           uint32_t* deg, unsigned long long* asym, hipStream_t);
-int ame_fill_missing_dispatch(const ame_dims*, const ame_fill_args*, hipStream_t);
-long long ame_mask_words_count(const ame_dims*);
-long long ame_fill_work_doubles(const ame_dims*);
-long long ame_fill_blocks(const ame_dims*);
 
 static thread_local char g_err[512] = "";
 

@@ -34,6 +34,7 @@
 // wide states, a blocked LDL^T on fp64 MFMA (ame_cov_mfma_kernel, further down;
 // DESIGN.md §4 K2, profiles/r05_cov_ab.txt).
 #include "ame_common.h"
+#include "ame_internal.h"
 #include "ame_wave.h"
 #include <type_traits>
 

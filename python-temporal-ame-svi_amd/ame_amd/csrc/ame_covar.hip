@@ -26,6 +26,7 @@
 // the same bits under any split of the slices over calls.  No atomics, no
 // waits, nothing of size n^2 written by K1 / K2.
 #include "ame_tile.h"
+#include "ame_internal.h"
 
 // doubles of one partial / output row: G (4 p) then H (4 p^2)
 __host__ __device__ constexpr int ame_covar_row(int p) { return 4 * p + 4 * p * p; }

@@ -16,6 +16,7 @@
 // (Y_ji = swap(Y_ij), checked by K0) only the upper-triangle tiles are read and
 // the mirror half of the reconstruction error is counted twice.
 #include "ame_tile.h"
+#include "ame_internal.h"
 #include "ame_sweep_dev.h"
 #include <type_traits>
 using namespace ame;
@@ -430,7 +431,7 @@ ame_pairs2_kernel(ame_dims dm, const float* __restrict__ Yt, const float* __rest
 #pragma unroll
     for (int q = 0; q < AHEAD; ++q) issue_y(q);
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * AHEAD) : "memory");   // staging of tile 0
-    lds_barrier3();   // LDS-only barrier: the Y prefetch stays in flight
+    lds_barrier();   // LDS-only barrier: the Y prefetch stays in flight
 
     // residual sufficient statistics, packed over two columns (v_pk_fma_f32):
     // pairs with i < j -> A00 = sum e0^2, A01 = sum e0 e1, A11 = sum e1^2;
@@ -533,7 +534,7 @@ ame_pairs2_kernel(ame_dims dm, const float* __restrict__ Yt, const float* __rest
         const double a11 = (double)A11.x + (double)A11.y;
         quad += p * a00 + qs * a01 + sr * a11;
         sq += (swap_mode ? 2.0 : 1.0) * (a00 + a11) + ((double)S.x + (double)S.y);
-        lds_barrier3();       // staging of tile tt+1 visible; stg[tt & 1] free
+        lds_barrier();       // staging of tile tt+1 visible; stg[tt & 1] free
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // dummy DMAs drained before exit
     double v2[2] = {quad, sq};

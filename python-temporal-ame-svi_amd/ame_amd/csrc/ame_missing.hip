@@ -27,6 +27,7 @@
 // has the same bits under any split of the slices over calls.  No atomics in
 // the floating-point sums, no waits between workgroups.
 #include "ame_tile.h"
+#include "ame_internal.h"
 
 #define AME_MS_NC 2     // correction sums per slice
 

@@ -17,6 +17,7 @@
 // Bandwidth-bound by design: the covariances are the only large read (4 d^2
 // bytes per node and slice) and nothing of that size is written.
 #include "ame_tile.h"
+#include "ame_internal.h"
 
 #define AME_MS_CHUNK 32                      // nodes per workgroup
 #define AME_MS_MAXD (2 + 2 * AME_MAX_R)      // 66

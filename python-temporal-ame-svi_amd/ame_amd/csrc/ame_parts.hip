@@ -1,25 +1,7 @@
 // Routes the r-dependent entry points of the split build (build.py compiles
 // ame_sweep.hip and ame_predict.hip in 3 parts, ame_sweep3.hip and ame_elbo.hip in 2; part p holds
 // the latent dims r with r % parts == p, ame_common.h) to the part that holds r.
-#include "ame_common.h"
-
-#define AME_DECL_SWEEP(P)                                                                 \
-    int ame_sweep_dispatch_p##P(const ame_dims*, const ame_sweep_args*, hipStream_t);     \
-    int ame_sweep_blocks_per_cu_p##P(int, int, int);                                      \
-    int ame_sweep_workers_fit_p##P(const ame_dims*, int);                                 \
-    int ame_predict_dispatch_p##P(const ame_dims*, const ame_predict_args*, hipStream_t);     \
-    int ame_mstep_dyad_dispatch_p##P(const ame_dims*, const ame_mstep_args*, double*, hipStream_t);
-AME_DECL_SWEEP(0)
-AME_DECL_SWEEP(1)
-AME_DECL_SWEEP(2)
-#define AME_DECL_2(P)                                                                     \
-    int ame_sweep3_dispatch_p##P(const ame_dims*, const ame_sweep_args*, hipStream_t);    \
-    int ame_sweep3_supported_p##P(int, int);                                              \
-    int ame_sweep3_blocks_per_cu_p##P(int, int);                                          \
-    int ame_sweep3_lds_p##P(int, int);                                                    \
-    int ame_elbo_dispatch_p##P(const ame_dims*, const ame_elbo_args*, hipStream_t, int);
-AME_DECL_2(0)
-AME_DECL_2(1)
+#include "ame_internal.h"
 
 int ame_sweep_dispatch(const ame_dims* dm, const ame_sweep_args* a, hipStream_t st) {
     switch (dm->r % 3) {

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "ame_tile.h"
+#include "ame_internal.h"
 
 #define AME_PKB 32       // K chunk in floats
 #define AME_PLD 34       // LDS row stride: 2 li + lq hits 32 distinct banks per half wave

@@ -1,25 +1,14 @@
 // Device self-test of the wave/LDS primitives the sweep kernel is built on
-// (ame_wave.h reduce-scatter, LDS-DMA placement).  Exported for the GPU test
+// (ame_wave.h reduce-scatter, ame_sweep_dev.h LDS-DMA placement).  Exported for the GPU test
 // suite only (tests/test_gpu_primitives.py); not part of include/ame_amd.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ame_wave.h"
+#include "ame_sweep_dev.h"
 
 using namespace ame;
 
 namespace {
-
-__device__ __forceinline__ void dma16t(const void* gsrc, uint32_t lds) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds) : "memory");
-}
-__device__ __forceinline__ void dma4t(const void* gsrc, uint32_t lds) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds) : "memory");
-}
 
 // out layout: [0..63] float idx, [64..127] float value, [128..191] double idx,
 // [192..255] double value (as float), [256..] DMA readback
@@ -41,9 +30,9 @@ __global__ void selftest_kernel(const float* src, float* out) {
     out[192 + lane] = (float)rd;
     // DMA: 2 KiB with dwordx4 at LDS offset 1024, 256 B with dword at offset 4096
     const uint32_t base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)smem);
-    dma16t(src + lane * 4, base + 1024);
-    dma16t(src + 256 + lane * 4, base + 2048);
-    dma4t(src + 600 + lane, base + 4096);
+    dma16(src + lane * 4, base + 1024);
+    dma16(src + 256 + lane * 4, base + 2048);
+    dma4(src + 600 + lane, base + 4096);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const float* l = (const float*)(smem + 1024);

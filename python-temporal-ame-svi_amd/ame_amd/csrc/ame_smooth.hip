@@ -47,6 +47,7 @@
 //  K4 ame_smooth_lag_kernel: lag_sum[t] += chunk partials of the fp64 X_t in
 //     fixed chunks of 32 nodes, chunk by chunk in node order.
 // No atomics in any sum, no waits between workgroups.
+#include "ame_internal.h"
 #include "ame_tile.h"   // ame_mask_row_words: the row layout of ame_pack_mask
 
 #define AME_SM_CHUNK 32    // nodes per lag_sum partial, rows per h workgroup

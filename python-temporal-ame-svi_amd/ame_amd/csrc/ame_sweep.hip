@@ -40,6 +40,7 @@
 //    slice's workgroup adds the partials in a fixed order plus nodes m-3, m-2
 //    (new means, LDS ring); node m-1 stays the Woodbury observation.
 #include "ame_common.h"
+#include "ame_internal.h"
 #include "ame_sweep_dev.h"
 
 #ifdef AME_STAMPS
@@ -154,23 +155,6 @@ extern "C" int ame_debug_read_stamps(unsigned long long* host, int count) {
 #define AME_MG_UNROLL 8   // GEMV rows in flight per thread when the slice is read from HBM
 #endif
 
-// Workgroup barrier that orders LDS only.  __syncthreads() lowers to a release
-// fence that waits vmcnt(0), exposing every in-flight prefetch load and every
-// covariance store at each barrier; here global traffic stays in flight across
-// phases (loads are waited for by the compiler at their first use; no other
-// wave of this workgroup reads what this kernel stores to global memory).
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Wave-0 multi-dot: lane L holds p[h][v] of state rows k = L + 64h < D (KH
 // rows per lane; KH = 2 only for D > 64); every lane gets all NV sums.  The
 // lane's rows are added, then one 64-lane reduce-scatter (permlane swaps +
@@ -192,37 +176,10 @@ __device__ __forceinline__ void wave_multidot(const double (&pv)[KH][NV], double
     int idx;
     const double s = ame::wave_reduce_scatter<NR>(v, lane, idx);
     if (idx < NR) sums[idx] = s;
-    wave_lds_sync();
+    ame::wave_lds_sync_fence();
 #pragma unroll
     for (int qq = 0; qq < NR; ++qq) out[qq] = sums[qq];
-    wave_lds_sync();
-}
-
-struct M22 {
-    double a, b, c, d;   // [[a b][c d]]
-};
-__device__ __forceinline__ M22 inv22(M22 m) {
-    const double id = 1.0 / (m.a * m.d - m.b * m.c);
-    return {m.d * id, -m.b * id, -m.c * id, m.a * id};
-}
-// Per-step 2x2 inverses of wave 0's Woodbury chain: the determinant's
-// reciprocal from v_rcp_f64 plus two Newton steps (as the v3 solver) -- a
-// shorter dependent chain than the IEEE division sequence, full fp64 accuracy
-// for these well-scaled determinants
-__device__ __forceinline__ M22 inv22_fast(M22 m) {
-    const double det = m.a * m.d - m.b * m.c;
-    double r = __builtin_amdgcn_rcp(det);
-    r = fma(r, fma(-det, r, 1.0), r);
-    r = fma(r, fma(-det, r, 1.0), r);
-    return {m.d * r, -m.b * r, -m.c * r, m.a * r};
-}
-
-// lower-triangle index e -> (k, m), m <= k
-__device__ __forceinline__ void tri_decode(int e, int& k, int& m) {
-    k = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-    if ((k + 1) * (k + 2) / 2 <= e) ++k;
-    if (k * (k + 1) / 2 > e) --k;
-    m = e - k * (k + 1) / 2;
+    ame::wave_lds_sync_fence();
 }
 
 // AR-term partition of the natural parameter (the sweep's AR threads): thread
@@ -258,20 +215,8 @@ __device__ __forceinline__ void set_slot(float (&mreg)[N], int sn, float val, bo
 // Pipelined launch (MODE 3, wait_epoch != 0): every workgroup of slice t -- the
 // slice's own and its GEMV workers -- reads the previous sweep's outputs for
 // slices t and t+1 (old means, covariances; slice t+1 also reads the hand-off
-// granules this sweep overwrites), so it starts only once that sweep flagged
-// both done: done[t], done[t+1] (done[T_local] when the next slice group
-// follows, AME_SWEEP_FLAG_NEXT_GROUP), or for the rank's last slice the right
-// rank's back-channel done word.  Same epoch window as ame_sweep3.hip: a flag
-// above wait_epoch cannot be current and sets AME_STATUS_STALE_EPOCH.
-// Thread 0 waits (ame_wait_prev_done: the wait rules of include/ame_amd.h);
-// `dead` is set on thread 0 when it failed or gave up.
-__device__ __forceinline__ void ame_v2_wait_prev(const ame_sweep_args& a, int t, int TL, int tg, bool back_rd,
-                                                 int nd /* n * d: the back channel's done word */,
-                                                 bool& dead, bool account) {
-    if (a.wait_epoch == 0u) return;
-    if (threadIdx.x == 0) ame::ame_wait_prev_done(a, t, TL, tg, back_rd, nd, dead, account);
-    __syncthreads();
-}
+// granules this sweep overwrites), so each starts with ame::wait_prev_sweep
+// (ame_sweep_dev.h: the done flags, the back channel and their epoch window).
 
 // GEMV worker (MODE 2): workgroup TL + t*AME_GW + g owns nodes
 // [g*NW, (g+1)*NW) of slice t, NW = ceil(n / AME_GW); wave q holds nodes
@@ -313,10 +258,10 @@ __device__ __forceinline__ void gemv_worker(const ame_dims& dm, const ame_sweep_
     __syncthreads();
     // MODE 3, pipelined launch: this worker's inputs (old means of slices t and
     // t+1) are the previous sweep's outputs -- wait for its done flags as the
-    // slice's workgroup does (ame_v2_wait_prev)
+    // slice's workgroup does
     const bool back_rd = (MODE == 3) && (a.wait_epoch != 0u) && (t == TL - 1) && (a.back_in != nullptr);
     if constexpr (MODE == 3) {
-        ame_v2_wait_prev(a, t, TL, dm.t_begin + t, back_rd, n * D, dead, false);   // the slice accounts
+        ame::wait_prev_sweep(a, t, TL, dm.t_begin + t, back_rd, n * D, dead, false);   // the slice accounts
         if (tid == 0 && dead) *wdead = 1u;
     }
     // Right-neighbour AR terms PhiTQi mu_{j,t+1}^old of this worker's nodes, for
@@ -466,7 +411,7 @@ __device__ __forceinline__ void gemv_worker(const ame_dims& dm, const ame_sweep_
         // LDS-only barriers in this loop: __syncthreads() would also wait for the
         // Y prefetch just issued and for the last partial's store (vmcnt(0)),
         // a full memory round trip per node
-        lds_barrier();
+        ame::lds_barrier();
         WSTAMP(2);
         // U_c -> h_V (z1), V -> h_U (z0); four independent chains
         float a4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -511,7 +456,7 @@ __device__ __forceinline__ void gemv_worker(const ame_dims& dm, const ame_sweep_
             red[q * PW + M2] = s0;
             red[q * PW + M2 + 1] = s1;
         }
-        lds_barrier();
+        ame::lds_barrier();
         if (tid < PW) {
             const float v = ((red[tid] + red[PW + tid]) + red[2 * PW + tid]) + red[3 * PW + tid];
             const uint32_t tag = (*wdead != 0u) ? 0u : ame_gw_tag(a.epoch, m);
@@ -651,9 +596,12 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
     const double p = a.rinv[0], s = a.rinv[3], q = 0.5 * (a.rinv[1] + a.rinv[2]);
     const double r00 = a.rinv[0], r01 = a.rinv[1], r10 = a.rinv[2], r11 = a.rinv[3];
     const float r00f = (float)r00, r01f = (float)r01, r10f = (float)r10, r11f = (float)r11;
-    M22 Rm;   // R = R_inv^-1, symmetrised
+    // R = R_inv^-1, symmetrised.  Written out, not ame::inv2s: for an asymmetric
+    // R_inv that form rounds the other off-diagonal product first (1 ulp)
+    ame::Mat2 Rm;
     {
-        Rm = inv22(M22{r00, r01, r10, r11});
+        const double id = 1.0 / (r00 * r11 - r01 * r10);
+        Rm = {r11 * id, -r01 * id, -r10 * id, r00 * id};
         Rm.b = Rm.c = 0.5 * (Rm.b + Rm.c);
     }
     const size_t DD = (size_t)D * D;
@@ -683,8 +631,8 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
     uint32_t* wdead = (uint32_t*)(scal + 62);
     // pipelined launch (MODE 3): the previous sweep's slices t, t+1 first
     if constexpr (PIPE)
-        ame_v2_wait_prev(a, tl, TL, tg, (a.wait_epoch != 0u) && (tl == TL - 1) && (a.back_in != nullptr), n * D,
-                         dead, true);
+        ame::wait_prev_sweep(a, tl, TL, tg, (a.wait_epoch != 0u) && (tl == TL - 1) && (a.back_in != nullptr),
+                             n * D, dead, true);
 
     // ------------------------------------------------------------------
     // init: slice state, P_0 = P_const + sum_{j != 0} F_j, K_0 = P_0^-1
@@ -739,13 +687,14 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
         __syncthreads();
         for (int e = tid; e < NLT; e += AME_NT) {
             int k, m;
-            tri_decode(e, k, m);
+            ame::tri_decode(e, k, m);
             const double acc = (k < 2) ? 0.0 : (m < 2) ? colsum[jcol(k)] : K[k * KS + m];
             const double v = p0_entry(k, m, acc);
             K[k * KS + m] = v;
             K[m * KS + k] = v;
         }
     } else {
+        // (U, V) in LDS: node-by-node sums, whose order is part of this mode's results
         if (tid < M2) {   // sum of squares over all nodes: ssq[c<R] = sum U_c^2, ssq[R+c] = sum V_c^2
             double acc = 0.0;
             for (int j = 0; j < n; ++j) {
@@ -756,7 +705,7 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
         }
         for (int e = tid; e < NLT; e += AME_NT) {
             int k, m;
-            tri_decode(e, k, m);
+            ame::tri_decode(e, k, m);
             double acc = 0.0;
             if (k >= 2) {
                 const int kc = jcol(k);
@@ -781,7 +730,7 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
         const double rinv = 1.0 / red[pv];
         for (int e = tid; e < NLT; e += AME_NT) {
             int k, m;
-            tri_decode(e, k, m);
+            ame::tri_decode(e, k, m);
             double v;
             if (k == pv && m == pv) v = -rinv;
             else if (k == pv) v = red[m] * rinv;
@@ -826,7 +775,7 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
     for (int qq = 0; qq < LTQ; ++qq) {
         const int e = tid + AME_NT * qq;
         int k = -1, m = -1;
-        if (e < NLT) tri_decode(e, k, m);
+        if (e < NLT) ame::tri_decode(e, k, m);
         lk[qq] = k;
         lm[qq] = m;
     }
@@ -846,7 +795,7 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
     // LDS-slot worker code path spilled)
     constexpr bool PH3B = AME_PH3_BLOCK && MODE != 3 && MODE != 4;
     int pkb = -1, pmb = -1;
-    if (PH3B && tid < Ph3<D>::NBT) tri_decode(tid, pkb, pmb);
+    if (PH3B && tid < Ph3<D>::NBT) ame::tri_decode(tid, pkb, pmb);
 
     // ---- helpers ----
     float2 ypf[AME_YPF];
@@ -1542,7 +1491,7 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
             if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         STAMPW(23, 128);
-        lds_barrier();   // B1
+        ame::lds_barrier();   // B1
         STAMP(1);
         // ---------------- phase 2 ----------------
         if (wave == 0) {
@@ -1612,9 +1561,9 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
                 constexpr int NR = (VAR == AME_GOOD || VAR == AME_NAIVE) ? 10 : 14;
                 wave_multidot<14, D, KH, NR>(pr, o, red, scal, lane);
                 STAMPW(8, 0);
-                M22 Mm = {Rm.a + o[0], Rm.b + 0.5 * (o[1] + o[2]), 0.0, Rm.d + o[3]};
+                ame::Mat2 Mm = {Rm.a + o[0], Rm.b + 0.5 * (o[1] + o[2]), 0.0, Rm.d + o[3]};
                 Mm.c = Mm.b;
-                M22 Mi = inv22_fast(Mm);
+                ame::Mat2 Mi = ame::inv2_fast(Mm);
                 Mi.b = Mi.c = 0.5 * (Mi.b + Mi.c);
                 // rows 0, 1 of W (J K[:,b] = (W0[b], W1[b])) live in lanes 0, 1 of h = 0
                 const double Wa00 = ame::lane_bcast(W0[0], 0), Wa01 = ame::lane_bcast(W0[0], 1);
@@ -1681,9 +1630,9 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
                     pr2[h][2] = jn1[h] * Xp0[h]; pr2[h][3] = jn1[h] * Xp1[h];
                 }
                 wave_multidot<4, D, KH>(pr2, o2, red, scal + 16, lane);
-                M22 Sm = {Rm.a - o2[0], Rm.b - 0.5 * (o2[1] + o2[2]), 0.0, Rm.d - o2[3]};
+                ame::Mat2 Sm = {Rm.a - o2[0], Rm.b - 0.5 * (o2[1] + o2[2]), 0.0, Rm.d - o2[3]};
                 Sm.c = Sm.b;
-                M22 Si = inv22_fast(Sm);
+                ame::Mat2 Si = ame::inv2_fast(Sm);
                 Si.b = Si.c = 0.5 * (Si.b + Si.c);
 #pragma unroll
                 for (int h = 0; h < KH; ++h) {
@@ -1781,7 +1730,7 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
             }
         }
         if (!WK && wave == 0 && i + 2 < n && has_next) prefetch_y(i + 2);
-        lds_barrier();   // B2
+        ame::lds_barrier();   // B2
         STAMP(2);
         // ---------------- phase 3 ----------------
         // WK: node i+1's natural parameter in one piece (its parts were written
@@ -1907,7 +1856,7 @@ ame_sweep_kernel(ame_dims dm, ame_sweep_args a) {
             y_prev0 = (float)scal[40];
             y_prev1 = (float)scal[41];
         }
-        lds_barrier();   // B3
+        ame::lds_barrier();   // B3
         STAMP(3);
     }
     cov_flush(n - 1);

@@ -42,24 +42,11 @@
 //    is then queued while this one runs, and consecutive sweeps overlap instead
 //    of each paying the wavefront fill.
 #include "ame_common.h"
+#include "ame_internal.h"
 #include "ame_wave.h"
 #include "ame_sweep_dev.h"
 
 using namespace ame;
-
-namespace {
-// 2x2 inverse with the reciprocal of the determinant from v_rcp_f64 plus two
-// Newton steps (instead of the IEEE division sequence): full fp64 accuracy for
-// the well-scaled determinants here, a shorter dependent chain
-__device__ __forceinline__ Mat2 inv2s_fast(Mat2 m) {
-    const double det = m.a * m.d - m.b * m.c;
-    double r = __builtin_amdgcn_rcp(det);
-    r = fma(r, fma(-det, r, 1.0), r);
-    r = fma(r, fma(-det, r, 1.0), r);
-    const double o = 0.5 * (-m.b * r - m.c * r);
-    return {m.d * r, o, o, m.a * r};
-}
-}  // namespace
 
 #ifdef AME_STAMPS
 // Diagnostic build only (cdna_hip_programming.md §7, in-kernel stamps): the
@@ -397,7 +384,7 @@ ame_sweep3_kernel(ame_dims dm, ame_sweep_args a) {
         __syncthreads();
         for (int e = tid; e < NLT; e += kNT) {
             int k, m;
-            tri_decode3(e, k, m);
+            tri_decode(e, k, m);
             double v;
             if (k < 2) {
                 v = ((k == 0 && m == 0) ? pp : (k == 1 && m == 1) ? ss : qq) * (double)(n - 1);
@@ -422,7 +409,7 @@ ame_sweep3_kernel(ame_dims dm, ame_sweep_args a) {
             const double rinv = 1.0 / piv[pv];
             for (int e = tid; e < NLT; e += kNT) {
                 int k, m;
-                tri_decode3(e, k, m);
+                tri_decode(e, k, m);
                 double v;
                 if (k == pv && m == pv) v = -rinv;
                 else if (k == pv) v = piv[m] * rinv;
@@ -769,7 +756,7 @@ ame_sweep3_kernel(ame_dims dm, ame_sweep_args a) {
                 const double sv = wave_reduce_scatter<NV>(pr, lane, idx);
                 if (idx < NV) red[idx] = sv;
             }
-            wave_lds_sync3();
+            wave_lds_sync_waitcnt();
             double o[NV];
 #pragma unroll
             for (int q = 0; q < NV; ++q) o[q] = red[q];
@@ -907,13 +894,13 @@ ame_sweep3_kernel(ame_dims dm, ame_sweep_args a) {
                 prep(i + 1);
                 STAMP3(9);
             }
-            lds_barrier3();
+            lds_barrier();
         }
         {
             const int i = n;
             PROG3();
         }
-        lds_barrier3();   // epilogue step n
+        lds_barrier();   // epilogue step n
     } else {
         // ============================ HELPERS ============================
         int lk[LTQ], lm[LTQ];
@@ -921,7 +908,7 @@ ame_sweep3_kernel(ame_dims dm, ame_sweep_args a) {
         for (int q = 0; q < LTQ; ++q) {
             const int e = hl + C::NHB * q;
             int k = -1, m = -1;
-            if (hl < C::NHB && e < NLT) tri_decode3(e, k, m);
+            if (hl < C::NHB && e < NLT) tri_decode(e, k, m);
             lk[q] = k;
             lm[q] = m;
         }
@@ -998,7 +985,7 @@ ame_sweep3_kernel(ame_dims dm, ame_sweep_args a) {
 #endif
                 gran_finish(i + 1, gv, muL + hw * 64);
                 STAMP3(2);
-                wave_lds_sync3();
+                wave_lds_sync_waitcnt();
                 hf1(i + 1);
                 STAMP3(3);
                 if (hw == 0) jn_fill(i + 2);   // J rows of node i+2 for the solver
@@ -1045,7 +1032,7 @@ ame_sweep3_kernel(ame_dims dm, ame_sweep_args a) {
             // this step)
             if (hw == 5 && i < n && lane < D) pring[(size_t)((i + 2) & 3) * 128 + lane] = pgr;
             STAMP3(9);
-            lds_barrier3();
+            lds_barrier();
         }
     }
     // the last node's new covariance (staged by HB in the epilogue step n)

@@ -1,23 +1,81 @@
-// Device helpers of the LDS-DMA kernels (ame_sweep3.hip, ame_sweep.hip,
-// ame_elbo.hip): workgroup-local hand-off counters in LDS, LDS-DMA
+// Device code shared by the sweep kernels (ame_sweep3.hip: kind 3,
+// ame_sweep.hip: kinds 20-24) and the other LDS-DMA kernels (ame_elbo.hip,
+// ame_selftest.hip).
+//
+// Shared by both sweeps: the pipelined entry wait on the previous sweep's done
+// flags and back channel (ame_wait_prev_done / wait_prev_sweep) and P_0's node
+// sums on fp64 MFMA (p0_gram_mfma).  The rest of the slice prologue (P_0's
+// entries, the in-place symmetric sweep), the granule wait for mu_{node, t-1}
+// and the slice-done epilogue are still written out in each kernel: moved
+// into functions here they changed register or SGPR-spill counts of some
+// instances, and with equal counts the v3 sweep measured 8 % slower
+// (DESIGN.md K1).
+//
+// Here: workgroup-local hand-off counters in LDS, LDS-only barriers, LDS-DMA
 // (global_load_lds) issue wrappers with manual vmcnt accounting, the packed
-// triangle index decode, the J entries of a node and two DPP pair-adds.
+// triangle index decode, the fast 2x2 inverse, the J entries of a node and two
+// DPP pair-adds.
 #pragma once
 #include "ame_common.h"
 #include "ame_wave.h"
 
 namespace ame {
 
-__device__ __forceinline__ void lds_barrier3() {
+// Workgroup barrier that orders LDS only.  __syncthreads() lowers to a release
+// fence that waits vmcnt(0), exposing every in-flight prefetch load, LDS-DMA and
+// covariance store at each barrier; here global traffic stays in flight across
+// phases (loads are waited for at their first use; no other wave of the
+// workgroup reads what a sweep kernel stores to global memory).
+__device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
-__device__ __forceinline__ void wave_lds_sync3() {
+// LDS hand-over inside one wave, in two forms that compile differently: an
+// explicit s_waitcnt lgkmcnt(0) (v3), or wavefront-scope fences that leave the
+// wait to the compiler (v2).
+__device__ __forceinline__ void wave_lds_sync_waitcnt() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
 }
+__device__ __forceinline__ void wave_lds_sync_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// lower-triangle index e -> (k, m), m <= k
+__device__ __forceinline__ void tri_decode(int e, int& k, int& m) {
+    k = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
+    if ((k + 1) * (k + 2) / 2 <= e) ++k;
+    if (k * (k + 1) / 2 > e) --k;
+    m = e - k * (k + 1) / 2;
+}
+
+// 2x2 inverse with the reciprocal of the determinant from v_rcp_f64 plus two
+// Newton steps (instead of the IEEE division sequence): full fp64 accuracy for
+// the well-scaled determinants of the solvers' per-step Woodbury chain, a
+// shorter dependent chain.  Two forms, because each solver loop keeps its
+// instruction stream: inv2s_fast symmetrises the off-diagonal inside (v3);
+// inv2_fast does not, for v2, whose call sites pass a symmetric matrix and
+// average the result's off-diagonals themselves (same values: with b == c the
+// two products are equal, but one multiply more per inverse).
+__device__ __forceinline__ Mat2 inv2_fast(Mat2 m) {
+    const double det = m.a * m.d - m.b * m.c;
+    double r = __builtin_amdgcn_rcp(det);
+    r = fma(r, fma(-det, r, 1.0), r);
+    r = fma(r, fma(-det, r, 1.0), r);
+    return {m.d * r, -m.b * r, -m.c * r, m.a * r};
+}
+__device__ __forceinline__ Mat2 inv2s_fast(Mat2 m) {
+    const double det = m.a * m.d - m.b * m.c;
+    double r = __builtin_amdgcn_rcp(det);
+    r = fma(r, fma(-det, r, 1.0), r);
+    r = fma(r, fma(-det, r, 1.0), r);
+    const double o = 0.5 * (-m.b * r - m.c * r);
+    return {m.d * r, o, o, m.a * r};
+}
+
 // LDS counters (workgroup-coherent); writers drain their LDS stores first.
 __device__ __forceinline__ void lds_signal_add(uint32_t* f, uint32_t v) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -117,6 +175,17 @@ __device__ __forceinline__ void ame_wait_prev_done(const ame_sweep_args& a, int 
     if (back_rd) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+// The same for a whole workgroup (all threads call it): thread 0 waits, `dead`
+// is set on thread 0 when the wait failed or gave up; no-op unless pipelined.
+// Workgroups that share a slice (the GEMV workers) pass account = false: the
+// slice's own workgroup counts the back-channel wait time.
+__device__ __forceinline__ void wait_prev_sweep(const ame_sweep_args& a, int t, int TL, int tg, bool back_rd,
+                                                int nd /* n * d: the back channel's done word */,
+                                                bool& dead, bool account) {
+    if (a.wait_epoch == 0u) return;
+    if (threadIdx.x == 0) ame_wait_prev_done(a, t, TL, tg, back_rd, nd, dead, account);
+    __syncthreads();
 }
 
 // ---- P_0's node sums on fp64 MFMA (sweep prologues, v3 and v2) ----
@@ -267,13 +336,6 @@ __device__ __forceinline__ void vm_wait_le(int n) {
     else if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-__device__ __forceinline__ void tri_decode3(int e, int& k, int& m) {
-    k = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-    if ((k + 1) * (k + 2) / 2 <= e) ++k;
-    if (k * (k + 1) / 2 > e) --k;
-    m = e - k * (k + 1) / 2;
 }
 
 // jcol in two halves, so the LDS read can be issued ahead of its use:

@@ -1,11 +1,13 @@
 """Bit-for-bit comparison of two library builds on one fit (GPU box).
 
-    AME_LIB_PATH=libA.so python tools/bitcmp.py save A.npz [n,T,r] [variant] [iters] [kind]
+    AME_LIB_PATH=libA.so python tools/bitcmp.py save A.npz [n,T,r] [variant] [iters] [kind] [opts]
     AME_LIB_PATH=libB.so python tools/bitcmp.py save B.npz ...
     python tools/bitcmp.py cmp A.npz B.npz
 
 A kernel change meant to keep every sum (same products, same order) must give
 equal means and covariances; `cmp` prints the first differing entries otherwise.
+kind: sweep kernel to request ("-" for the engine's choice); opts: further engine
+options as key=int pairs, e.g. slice_group=2 (several slice groups per sweep).
 """
 import os
 import sys
@@ -16,14 +18,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "python-temporal-ame-svi_amd"))
 
 
-def save(path, shape="4096,4,32", variant="good", iters="2", kind=None):
+def save(path, shape="4096,4,32", variant="good", iters="2", kind=None, opts_str=""):
     import torch
     from ame_amd import TemporalAMEModel, TemporalAMENaiveMFVI, TemporalAMEStructuredMFVI
     n, T, r = (int(x) for x in shape.split(","))
     dev = torch.device("cuda", 0)
     m = TemporalAMEModel(n, T, r, seed=5)
     m.generate_data_fast(seed=6)
-    opts = {} if kind is None else {"sweep_kernel": int(kind)}
+    opts = {} if kind in (None, "-") else {"sweep_kernel": int(kind)}
+    opts.update((k, int(v)) for k, v in (kv.split("=") for kv in opts_str.split(",") if kv))
     if variant == "naive":
         vi = TemporalAMENaiveMFVI(m, learning_rate=0.5, device=dev, engine_options=opts)
     else:
