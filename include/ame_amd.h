@@ -42,6 +42,10 @@
  *   ame_pack_mask,    replace nothing in the reference: partially observed
  *   ame_fill_missing  networks (the packed mask of hidden pairs; the working
  *                     network the sweep and the ELBO kernels read in their place).
+ *   ame_net_moments,  replace nothing in the reference: goodness of fit by network
+ *   ame_net_triads,   statistics (row / column heterogeneity, reciprocity, cycles,
+ *   ame_simulate      transitivity) of the observed network and of networks
+ *                     simulated from the fitted states.
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -586,6 +590,81 @@ int ame_pack_mask(const uint8_t* M, uint64_t* Mt, const ame_dims* dims, uint64_t
 int ame_fill_missing(const ame_dims* dims, const ame_fill_args* args, void* stream);
 /* Scratch doubles ame_fill_missing needs (2 per tile), -1 on bad dims. */
 long long ame_fill_work_size(const ame_dims* dims);
+
+/* ---- goodness of fit: network statistics and simulated networks --------------------
+ * Replaces nothing the reference computes.  The posterior-predictive check of
+ * AME models compares five statistics of the observed network with those of
+ * networks simulated from the fit.  For one slice, y_ij = Yt[t][i][j][0] (i != j;
+ * the diagonal and the pad pair of odd n are never read as data), N = n (n - 1),
+ *   ybar = sum y / N,   s^2 = sum (y - ybar)^2 / (N - 1),   E = Y - ybar off the diagonal,
+ *   sd_rowmean, sd_colmean   sample sd over i of row_i / (n - 1), col_i / (n - 1)
+ *   dyad_dep                 correlation of (y_ij, y_ji) over ordered pairs
+ *   cycle_dep, trans_dep     tr(E E E), tr(E E' E) over n (n - 1) (n - 2) s^3
+ * Row i of Yt also holds y_ji = Yt[t][i][j][1]: the kernels read it there, so the
+ * network must be swap-consistent (ame_pack_y's mismatch count is 0).  The three
+ * entry points return raw fp64 sums; the host finishes the statistics.
+ * dims.t_begin / T_total / variant are only range-checked by the first two; a
+ * slice's output has the same bits under any split of the slices over calls and
+ * from run to run (fixed tiles, fixed orders, no atomics, no waits).
+ *
+ * ame_net_moments: one streaming pass, one wave per (slice, row), every sum fp64
+ * (products of fp32 values are exact):
+ *   node[t][i]  = { row_i = sum_{j != i} y_ij,  col_i = sum_{j != i} y_ji }
+ *   slice[t]    = { sum y_ij^2,  sum y_ij y_ji }  over ordered pairs i != j
+ * (the row partials of `slice` are added by ame_tile_sum_kernel, rows in order).
+ *
+ * ame_net_triads: with e = y - center[t] formed in fp32 (zero on the diagonal),
+ *   tri[t] = { sum_{i != j} (E E)_ij E_ji,  sum_{i != j} (E E')_ij E_ji }
+ * One workgroup per (slice, 128 x 128 output tile) walks k in chunks of 32; per
+ * chunk three operand panels are staged in LDS from the float2 rows (rows I
+ * entry [0] = E_ik, rows J entry [1] = E_kj, rows J entry [0] = E_jk; diagonal,
+ * k >= n and rows >= n zeroed, centre subtracted) and two sets of
+ * v_mfma_f32_32x32x2_f32 accumulators share the A operand.  The epilogue
+ * multiplies by E_ji in fp64; tile partials are added in tile order.  The n x n
+ * products are never written.  `center` is an input so that a reference can
+ * centre by the same fp32 number.
+ *
+ * ame_simulate: one network from one set of states x = [a, b, U, V],
+ *   Yt_out[t][i][j] = (mu_ij + eps_0, mu_ji + eps_1),  Yt_out[t][j][i] its swap, i < j,
+ *   mu_ij = a_i + b_j + u_i.v_j on fp32 MFMA (K order [a, 1, u], zero-padded to 4),
+ *   eps = (l00 z0, l10 z0 + l11 z1),  lr = { l00, l10, l11 } the lower Cholesky
+ *   factor of the noise covariance (zeros: the mean alone),
+ * the diagonal and the pad pair written as zero.  (z0, z1) of pair i < j of global
+ * slice t come from Philox4x32-10 with key = (seed low, seed high) and counter =
+ * (i, j, t, sample): w0, w1 of the output give u = (float(w >> 8) + 0.5f) * 2^-24
+ * (fp32 operations) and z0 = rad cos(2 pi u2), z1 = rad sin(2 pi u2),
+ * rad = sqrt(-2 log u1), in fp32 with the accurate library functions; eps and
+ * the sum with mu are formed in fp64 and rounded to fp32 once.  The counter
+ * names the dyad: the same bits for any slice split and any t_begin that keeps
+ * t_begin + tl.  Both triangles are written in row segments (the tile is
+ * staged in LDS). */
+typedef struct ame_moments_args {
+    const float* Yt;       /* [T_local][n][ny][2] packed network                       */
+    double* node;          /* [T_local][n][2] fp64: row_i, col_i                       */
+    double* slice;         /* [T_local][2] fp64: sum y^2, sum y_ij y_ji                */
+    double* work;          /* >= ame_net_moments_work_size() doubles                   */
+    uint64_t work_doubles; /* size of `work` in doubles, checked                       */
+} ame_moments_args;
+typedef struct ame_triads_args {
+    const float* Yt;       /* [T_local][n][ny][2] packed network, 16-byte aligned      */
+    const float* center;   /* [T_local] fp32, subtracted from every off-diagonal entry */
+    double* tri;           /* [T_local][2] fp64: cycle sum, transitive sum             */
+    double* work;          /* >= ame_net_triads_work_size() doubles                    */
+    uint64_t work_doubles; /* size of `work` in doubles, checked                       */
+} ame_triads_args;
+typedef struct ame_simulate_args {
+    const float* x;        /* [T_local][n][d] one draw of the states (or the means)    */
+    double lr[3];          /* l00, l10, l11 of the noise covariance's Cholesky factor  */
+    uint64_t seed;         /* Philox key                                               */
+    uint32_t sample;       /* Philox counter word 3                                    */
+    float* Yt_out;         /* [T_local][n][ny][2], 16-byte aligned                     */
+} ame_simulate_args;
+int ame_net_moments(const ame_dims* dims, const ame_moments_args* args, void* stream);
+int ame_net_triads(const ame_dims* dims, const ame_triads_args* args, void* stream);
+int ame_simulate(const ame_dims* dims, const ame_simulate_args* args, void* stream);
+/* Scratch doubles: 2 per (slice, row) / 2 per (slice, 128 x 128 tile); -1 on bad dims. */
+long long ame_net_moments_work_size(const ame_dims* dims);
+long long ame_net_triads_work_size(const ame_dims* dims);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

@@ -553,6 +553,63 @@ int ame_covar_resid(const ame_dims* dims, const float* Yt_raw, const float* Wt, 
                     "covar_resid");
 }
 
+long long ame_net_moments_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_net_moments_work_doubles(dims);
+}
+
+long long ame_net_triads_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_net_triads_work_doubles(dims);
+}
+
+int ame_net_moments(const ame_dims* dims, const ame_moments_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_net_moments: args is NULL");
+    if (!a->Yt || !a->node || !a->slice || !a->work)
+        return fail("ame_net_moments: NULL buffer (Yt, node, slice, work)");
+    if ((uintptr_t)a->Yt & 15) return fail("ame_net_moments: Yt must be 16-byte aligned");
+    if (((uintptr_t)a->node | (uintptr_t)a->slice | (uintptr_t)a->work) & 7)
+        return fail("ame_net_moments: node, slice and work must be 8-byte aligned");
+    if ((long long)a->work_doubles < ame_net_moments_work_doubles(dims))
+        return fail("ame_net_moments: work holds fewer doubles than ame_net_moments_work_size");
+    if (ame_net_moments_blocks(dims) > 0x7FFFFFFFLL)
+        return fail("ame_net_moments: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_net_moments_dispatch(dims, a, (hipStream_t)stream), "net_moments");
+}
+
+int ame_net_triads(const ame_dims* dims, const ame_triads_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_net_triads: args is NULL");
+    if (!a->Yt || !a->center || !a->tri || !a->work)
+        return fail("ame_net_triads: NULL buffer (Yt, center, tri, work)");
+    if ((uintptr_t)a->Yt & 15) return fail("ame_net_triads: Yt must be 16-byte aligned");
+    if ((uintptr_t)a->center & 3) return fail("ame_net_triads: center must be 4-byte aligned");
+    if (((uintptr_t)a->tri | (uintptr_t)a->work) & 7)
+        return fail("ame_net_triads: tri and work must be 8-byte aligned");
+    if ((long long)a->work_doubles < ame_net_triads_work_doubles(dims))
+        return fail("ame_net_triads: work holds fewer doubles than ame_net_triads_work_size");
+    if (ame_net_triads_blocks(dims) > 0x7FFFFFFFLL)
+        return fail("ame_net_triads: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_net_triads_dispatch(dims, a, (hipStream_t)stream), "net_triads");
+}
+
+int ame_simulate(const ame_dims* dims, const ame_simulate_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_simulate: args is NULL");
+    if (!a->x || !a->Yt_out) return fail("ame_simulate: NULL buffer (x, Yt_out)");
+    if ((uintptr_t)a->x & 3) return fail("ame_simulate: x must be 4-byte aligned");
+    if ((uintptr_t)a->Yt_out & 15) return fail("ame_simulate: Yt_out must be 16-byte aligned");
+    if (!(a->lr[0] == a->lr[0] && a->lr[1] == a->lr[1] && a->lr[2] == a->lr[2]))
+        return fail("ame_simulate: lr holds a NaN");
+    if (ame_simulate_blocks(dims) > 0x7FFFFFFFLL)
+        return fail("ame_simulate: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_simulate_dispatch(dims, a, (hipStream_t)stream), "simulate");
+}
+
 long long ame_smooth_work_size(const ame_dims* dims, int nodes) {
     if (check_dims(dims)) return -1;
     if (nodes < 1 || nodes > dims->n) return fail("ame_smooth_work_size: nodes=%d outside [1, n]", nodes);

@@ -67,5 +67,14 @@ int ame_fill_missing_dispatch(const ame_dims*, const ame_fill_args*, hipStream_t
 long long ame_mask_words_count(const ame_dims*);
 long long ame_fill_work_doubles(const ame_dims*);
 long long ame_fill_blocks(const ame_dims*);
+// ame_gof.hip
+int ame_net_moments_dispatch(const ame_dims*, const ame_moments_args*, hipStream_t);
+int ame_net_triads_dispatch(const ame_dims*, const ame_triads_args*, hipStream_t);
+int ame_simulate_dispatch(const ame_dims*, const ame_simulate_args*, hipStream_t);
+long long ame_net_moments_work_doubles(const ame_dims*);
+long long ame_net_moments_blocks(const ame_dims*);
+long long ame_net_triads_work_doubles(const ame_dims*);
+long long ame_net_triads_blocks(const ame_dims*);
+long long ame_simulate_blocks(const ame_dims*);
 
 #undef AME_SPLIT_FN

@@ -408,6 +408,7 @@ class DeviceEngine:
         # and none keeps a result there -- outputs are separate tensors, also
         # those of smooth() that are fed back into mstep_stats / predict.
         self._side_work = None
+        self._sim_buf = None    # one slice chunk of a simulated network (simulated_statistics)
         self._host_ready = None
         # test hook only (tests/test_gpu_stale_epoch.py): False lets a pipelined
         # launch skip the wait for host-issued writes, to show the device's
@@ -1062,6 +1063,116 @@ class DeviceEngine:
                 _lib.check(self.L.ame_mstep_stats(ctypes.byref(dm), ctypes.byref(a), sp),
                            "ame_mstep_stats")
         return state, dyad
+
+    # ------------------------------------------------------------------
+    # goodness of fit (ame_net_moments / ame_net_triads / ame_simulate)
+    # ------------------------------------------------------------------
+    def _check_packed(self, Yt, what):
+        S = int(Yt.shape[0])
+        assert tuple(Yt.shape) == (S, self.n, self.ny, 2) and Yt.dtype == torch.float32 \
+            and Yt.is_contiguous(), f"{what}: a packed [S][n][ny][2] fp32 network is expected"
+        return S
+
+    def net_moments(self, Yt):
+        """ame_net_moments over a packed stack Yt [S][n][ny][2]: ``node`` [S][n][2]
+        (row_i, col_i) and ``slice`` [S][2] (sum y^2, sum y_ij y_ji), fp64 on the
+        device.  Whole slices at a time within the scratch budget of predict();
+        a slice's rows do not depend on the split.  Runs on the ELBO stream."""
+        S = self._check_packed(Yt, "net_moments")
+        chunk, wk = self._slice_chunk(self.L.ame_net_moments_work_size, S)
+        with torch.cuda.device(self.dev):
+            node = torch.empty(S, self.n, 2, dtype=torch.float64, device=self.dev)
+            sl = torch.empty(S, 2, dtype=torch.float64, device=self.dev)
+        with self._elbo_call("net_moments") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(self.n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_moments_args(Yt=_ptr(Yt[s0:s1]), node=_ptr(node[s0:s1]), slice=_ptr(sl[s0:s1]),
+                                          work=_ptr(wk), work_doubles=wk.numel())
+                _lib.check(self.L.ame_net_moments(ctypes.byref(dm), ctypes.byref(a), sp), "ame_net_moments")
+        for t in (Yt, wk, node, sl):
+            t.record_stream(self._elbo_stream())
+        return node, sl
+
+    def net_triads(self, Yt, center):
+        """ame_net_triads over a packed stack Yt [S][n][ny][2] centred by
+        ``center`` [S] (fp32, device): ``tri`` [S][2] fp64 on the device, the
+        cycle and the transitive sum.  Chunked as net_moments."""
+        S = self._check_packed(Yt, "net_triads")
+        assert tuple(center.shape) == (S,) and center.dtype == torch.float32 and center.is_contiguous()
+        chunk, wk = self._slice_chunk(self.L.ame_net_triads_work_size, S)
+        with torch.cuda.device(self.dev):
+            tri = torch.empty(S, 2, dtype=torch.float64, device=self.dev)
+        with self._elbo_call("net_triads") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(self.n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_triads_args(Yt=_ptr(Yt[s0:s1]), center=_ptr(center[s0:s1]), tri=_ptr(tri[s0:s1]),
+                                         work=_ptr(wk), work_doubles=wk.numel())
+                _lib.check(self.L.ame_net_triads(ctypes.byref(dm), ctypes.byref(a), sp), "ame_net_triads")
+        for t in (Yt, center, wk, tri):
+            t.record_stream(self._elbo_stream())
+        return tri
+
+    def net_statistics(self, Yt):
+        """The raw sums of the five network statistics of a packed stack (which
+        must be swap-consistent): {"node", "slice", "tri", "center"} on the
+        device, for :func:`ame_amd.gof.combine`.  The centre of the triad sums is
+        the mean of the network rounded to fp32, formed on the device from the
+        row sums (no host round trip)."""
+        node, sl = self.net_moments(Yt)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            center = (node[:, :, 0].sum(dim=1) / float(self.n * (self.n - 1))).float().contiguous()
+        tri = self.net_triads(Yt, center)
+        return {"node": node, "slice": sl, "tri": tri, "center": center}
+
+    def sim_chunk(self):
+        """Slices of one simulated-network buffer: whole slices within the bytes of
+        predict()'s scratch budget."""
+        per = self.n * self.ny * 2 * 4
+        return max(1, min(self.shard.T_local, self.PREDICT_WORK_DOUBLES * 8 // per))
+
+    def simulate(self, x, noise_chol, seed, sample, out=None, t_begin=0):
+        """ame_simulate: one network from the states x [S][n][d] (device, fp32,
+        contiguous) of the global slices t_begin .. t_begin + S - 1 into ``out``
+        [S][n][ny][2] (allocated when None).  noise_chol = (l00, l10, l11), the
+        lower Cholesky factor of the noise covariance; zeros give the mean.  The
+        Philox counter names (i, j, global slice, sample): the bits do not depend
+        on how the slices are split over calls."""
+        S = int(x.shape[0])
+        assert tuple(x.shape) == (S, self.n, self.d) and x.dtype == torch.float32 and x.is_contiguous()
+        if out is None:
+            with torch.cuda.device(self.dev):
+                out = torch.empty(S, self.n, self.ny, 2, dtype=torch.float32, device=self.dev)
+        assert self._check_packed(out, "simulate") == S
+        l3 = (ctypes.c_double * 3)(*(float(v) for v in noise_chol))
+        dm = _lib.ame_dims(self.n, self.r, S, int(t_begin), int(t_begin) + S, self.vcode)
+        a = _lib.ame_simulate_args(x=_ptr(x), lr=l3, seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   sample=int(sample) & 0xFFFFFFFF, Yt_out=_ptr(out))
+        with self._elbo_call("simulate") as sp:
+            _lib.check(self.L.ame_simulate(ctypes.byref(dm), ctypes.byref(a), sp), "ame_simulate")
+        for t in (x, out):
+            t.record_stream(self._elbo_stream())
+        return out
+
+    def simulated_statistics(self, x, noise_chol, seed, sample):
+        """The raw sums (as net_statistics, on the host) of one network simulated
+        from the states x [T_local][n][d], slice chunk by slice chunk through one
+        reused buffer of sim_chunk() slices: no n^2 T allocation."""
+        TL, chunk = int(x.shape[0]), self.sim_chunk()
+        if self._sim_buf is None or self._sim_buf.shape[0] != chunk:
+            with torch.cuda.device(self.dev):
+                self._sim_buf = torch.empty(chunk, self.n, self.ny, 2, dtype=torch.float32, device=self.dev)
+        parts = []
+        for s0 in range(0, TL, chunk):
+            s1 = min(TL, s0 + chunk)
+            buf = self._sim_buf[:s1 - s0]
+            self.simulate(x[s0:s1], noise_chol, seed, sample, out=buf, t_begin=self.shard.t_begin + s0)
+            raw = self.net_statistics(buf)
+            # the copy ends before the buffer is simulated into again
+            with torch.cuda.stream(self.stream):
+                parts.append({k: v.cpu() for k, v in raw.items()})
+        return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
 
     # ------------------------------------------------------------------
     # exact per-node smoothing across time (ame_smooth)

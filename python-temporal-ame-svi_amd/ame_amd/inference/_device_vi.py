@@ -621,6 +621,114 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
                       f"{res['objective_after']:.4f} | ELBO: {float(self.history['elbo'][-1]):10.2f}")
         return self.history
 
+    # ---------------- goodness of fit by network statistics (extension) ----------------
+    def _gof_engine(self):
+        """The engine, after the refusals of the goodness-of-fit calls (raised
+        before anything is launched for them)."""
+        if self._time_sharded():
+            raise NotImplementedError("network statistics are not available on a time-sharded run: "
+                                      "every rank would simulate and reduce its own slices only")
+        if getattr(self.model, "missing", None) is not None:
+            raise NotImplementedError("network statistics are not available with missing dyads: a hidden "
+                                      "pair has no observed value (the complete-case statistics are not "
+                                      "implemented)")
+        eng = self._predict_engine()
+        if not eng.swap_consistent:
+            raise ValueError("network statistics need a swap-consistent network: Y[j, i, t] must be "
+                             "Y[i, j, t] with its two entries exchanged (the kernels read y_ji from row i)")
+        return eng
+
+    @staticmethod
+    def _stat_dict(raw, n):
+        from .. import gof as G
+        return G.combine(raw["node"].cpu().numpy(), raw["slice"].cpu().numpy(), raw["tri"].cpu().numpy(), n)
+
+    def network_statistics(self) -> dict:
+        """The five network statistics of the GOF panel of ``amen``, per slice, of
+        the network the fit reads: fp64 (T,) arrays ``sd_rowmean``,
+        ``sd_colmean``, ``dyad_dep``, ``cycle_dep``, ``trans_dep``, plus ``mean``
+        and ``sd`` (:mod:`ame_amd.gof`).  With covariates that network is the
+        residual Y - sum_k beta_k W_k at the current beta, so the statistics are
+        the residual's.  Needs a fully observed, swap-consistent network; not
+        available on a time-sharded run.  Does not modify this object."""
+        eng = self._gof_engine()
+        return self._stat_dict(eng.net_statistics(eng.Yt), self.n)
+
+    @staticmethod
+    def _factor(cov):
+        """Lower Cholesky factors of [T][n][d][d] covariances (symmetrised), fp32
+        on the covariances' device: factored there when this torch build can,
+        otherwise on the CPU in fp64."""
+        c = 0.5 * (cov + cov.transpose(-1, -2))
+        try:
+            return torch.linalg.cholesky(c)
+        except RuntimeError:
+            return torch.linalg.cholesky(c.to("cpu", torch.float64)).to(cov.device, torch.float32)
+
+    def _state_draws(self, n_sim, seed, smoothed):
+        """Generator of n_sim draws [T][n][d] (device, fp32) from q: every (node,
+        slice) an independent N(m, S).  The statistics are per slice and q
+        factorises over nodes, so the time marginals are all they need."""
+        eng, x, cov, _ = self._state(smoothed)
+        L = self._factor(cov)
+        g = torch.Generator(device=x.device)
+        g.manual_seed(int(seed))
+        for _ in range(int(n_sim)):
+            z = torch.randn(x.shape, generator=g, device=x.device, dtype=torch.float32)
+            yield (x + torch.einsum("tnij,tnj->tni", L, z)).contiguous()
+
+    def sample_states(self, n_sim: int, seed: int = 0, smoothed=False) -> torch.Tensor:
+        """``n_sim`` draws (n_sim, n, T, d) of the states from q (CPU fp32): every
+        (node, slice) is an independent N(m, S) from a Cholesky factor of its
+        covariance block, drawn with a seeded generator (the same seed gives the
+        same draws).  smoothed=True draws from the smoothed marginals
+        (:meth:`smooth`); the lag-one correlations are not reproduced, which no
+        per-slice statistic can see."""
+        if self._time_sharded():
+            raise NotImplementedError("sample_states is not available on a time-sharded run")
+        draws = [xk.permute(1, 0, 2).to("cpu") for xk in self._state_draws(n_sim, seed, smoothed)]
+        return torch.stack(draws).contiguous()
+
+    def gof(self, n_sim: int = 100, seed: int = 0, smoothed=False, states=None,
+            include_noise: bool = True) -> dict:
+        """Goodness of fit: the five network statistics (:meth:`network_statistics`)
+        of the observed network against those of ``n_sim`` networks simulated
+        from the fit, y_ij = mu_ij(x) + eps with x drawn from q
+        (:meth:`sample_states`; smoothed=True from the smoothed marginals) and
+        eps ~ N(0, sym(R)) (include_noise=False: mu alone).  Returns ``names``,
+        ``observed`` (T, 5), ``simulated`` (n_sim, T, 5) and ``quantile`` (T, 5),
+        the share of simulations at or below the observed value.  ``states``
+        (n_sim, n, T, d) replaces the internal draws; ``seed`` also keys the
+        noise (Philox counter: pair, slice, simulation).  With covariates the
+        observed network is the residual and the simulated ones are residual
+        networks too (mu + eps, no beta W).  Needs a fully observed,
+        swap-consistent network; not available on a time-sharded run.  Does not
+        modify this object."""
+        import numpy as np
+        from .. import gof as G
+        eng = self._gof_engine()
+        if states is not None:
+            states = torch.as_tensor(states)
+            if states.dim() != 4 or tuple(states.shape[1:]) != (self.n, self.T, self.d):
+                raise ValueError(f"states have shape {tuple(states.shape)}, expected "
+                                 f"(n_sim, {self.n}, {self.T}, {self.d})")
+            n_sim = int(states.shape[0])
+            draws = (states[k].detach().float().permute(1, 0, 2).to(eng.dev).contiguous()
+                     for k in range(n_sim))
+        else:
+            draws = self._state_draws(n_sim, seed, smoothed)
+        chol = (0.0, 0.0, 0.0)
+        if include_noise:
+            R = self.model.R.detach().to("cpu", torch.float64)
+            Lr = torch.linalg.cholesky(0.5 * (R + R.T))
+            chol = (float(Lr[0, 0]), float(Lr[1, 0]), float(Lr[1, 1]))
+        observed = G.stack(self._stat_dict(eng.net_statistics(eng.Yt), self.n))
+        sims = [G.stack(self._stat_dict(eng.simulated_statistics(xk, chol, seed, k), self.n))
+                for k, xk in enumerate(draws)]
+        simulated = np.stack(sims) if sims else np.zeros((0,) + observed.shape)
+        return {"names": G.NAMES, "observed": observed, "simulated": simulated,
+                "quantile": G.quantile(observed, simulated) if sims else np.full(observed.shape, np.nan)}
+
     def get_variational_means(self) -> torch.Tensor:
         return self.X_mean
 
