@@ -46,6 +46,9 @@
  *   ame_net_triads,   statistics (row / column heterogeneity, reciprocity, cycles,
  *   ame_simulate      transitivity) of the observed network and of networks
  *                     simulated from the fitted states.
+ *   ame_probit_fill,  replace nothing in the reference: binary networks with a
+ *   ame_probit_score  probit link (the working network the sweep reads in place of
+ *                     a 0 / 1 network; Bernoulli scores of held-out links).
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -665,6 +668,81 @@ int ame_simulate(const ame_dims* dims, const ame_simulate_args* args, void* stre
 /* Scratch doubles: 2 per (slice, row) / 2 per (slice, 128 x 128 tile); -1 on bad dims. */
 long long ame_net_moments_work_size(const ame_dims* dims);
 long long ame_net_triads_work_size(const ame_dims* dims);
+
+/* ---- binary networks: probit working network and link scoring ------------------------
+ * Replaces nothing the reference computes: it is Gaussian only.  The model is
+ *   z_pair = (z_ij, z_ji) ~ N(mu_pair, [[1, rho], [rho, 1]]),  y = 1[z > 0],  s = 2 y - 1
+ * (the noise scale is not identified).  q(z_ij) q(z_ji) are truncated normals that
+ * depend on q(x) only through m = E[mu_pair] = (a_i + b_j + u_i.v_j, a_j + b_i + u_j.v_i).
+ * With sd = sqrt(1 - rho^2) and kappa(x) = phi(x) / Phi(x): e = m + s kappa(s m), then
+ * AME_PROBIT_STEPS times (a constant; one code path for every rho, 0 included)
+ *   eta0 = m0 + rho (e1 - m1),  e0 = eta0 + s0 sd kappa(s0 eta0 / sd)
+ *   eta1 = m1 + rho (e0 - m0),  e1 = eta1 + s1 sd kappa(s1 eta1 / sd)
+ * and with d = e - m, x_a = s_a eta_a / sd the pair's part of the bound is
+ *   l = 1/2 log(1 - rho^2) - 1/2 d' R^-1 d + sum_a [ log Phi(x_a) + 1/2 kappa(x_a)^2 ]
+ * (<= the log orthant probability for any number of steps; sum_a log Phi(s_a m_a)
+ * at rho = 0).  The sweep reads row i's entry as J_j x_i + noise and never takes
+ * the partner's additive effects off (see missing dyads above), so the working
+ * network holds each node's own-perspective mean plus the correction d:
+ *   Yt[t][i][j] = (a_i + p + d0, b_i + q + d1),   Yt[t][j][i] = (a_j + q + d1, b_j + p + d0),
+ *   p = u_i.v_j, q = u_j.v_i.
+ * A hidden pair (Mt) gets d = 0, bit for bit what ame_fill_missing writes, and is
+ * left out of every sum.
+ *
+ * ame_probit_fill: Bt is packed by ame_pack_mask itself from B (uint8 [n][n][T],
+ * B[i][j][t] != 0 = the tie i -> j): bit j of row i is the tie i -> j.  B need not be
+ * symmetric; ame_pack_mask's pairs / deg / asym of it mean nothing.  One workgroup
+ * per (slice, 64 x 64 tile of the upper triangle), ame_fill_missing's tile order
+ * and slice mapping, no early return: every pair i < j is written.  p and q run on
+ * fp32 MFMA; everything from m on is fp64 (m0 = (double)a_i + (double)b_j +
+ * (double)p, kappa(x) = sqrt(2 / pi) / erfcx(-x / sqrt 2), log Phi(x) =
+ * log(erfcx(-x / sqrt 2) / 2) - x^2 / 2 for x < 0 and log1p(-erfc(x / sqrt 2) / 2)
+ * otherwise); a stored value is (float)((double)a_i + (double)p + d0), rounded
+ * once.  The tile is staged in LDS and both triangles are written in row segments.
+ * The diagonal, the pad column of odd n and rows >= n are never written.  Per slice
+ *   stat[t][0] = observed pairs i < j          stat[t][1] = sum l
+ *   stat[t][2] = sum over both entries of (y - Phi(m))^2
+ *   stat[t][3] = sum over both entries of log Phi(s m)
+ * tile partials added in tile order by a second kernel: no atomics, no waits, the
+ * same bits from run to run, for any split of the slices over calls and for both
+ * slice mappings (dims.t_begin / T_total / variant are only range-checked).
+ *
+ * ame_probit_score: ame_predict's feature rows and tile products with a Bernoulli
+ * epilogue.  Per pair i < j selected by Mt / mask_select exactly as in ame_predict's
+ * scoring, and for both entries, pi = Phi(E[mu] / sqrt(1 + V0)), the exact marginal
+ * P(y = 1) under q (V0 as under ame_predict); the observation is y = Yt > 1/2 of a
+ * 0 / 1 network.  Per slice, fp64, fixed-order reduce:
+ *   [0] pairs   [1] sum log pi(y)   [2] sum (y - pi)^2
+ *   [3] entries with (pi > 1/2) == y   [4] ties (y = 1)   [5] sum pi */
+#define AME_PROBIT_STEPS 2
+#define AME_PROBIT_STATS 4
+#define AME_PROBIT_SUMS 6
+typedef struct ame_probit_fill_args {
+    const float* x;        /* [T_local][n][d] means                                     */
+    const uint64_t* Bt;    /* [T_local][n][nw] packed ties (ame_pack_mask of B)         */
+    const uint64_t* Mt;    /* [T_local][n][nw] packed mask of hidden pairs, or NULL     */
+    double rho;            /* |rho| < 1                                                 */
+    float* Yt;             /* [T_local][n][ny][2] working network, every pair written   */
+    double* stat;          /* [T_local][AME_PROBIT_STATS] fp64                          */
+    double* work;          /* >= ame_probit_fill_work_size() doubles                    */
+    uint64_t work_doubles; /* size of `work` in doubles, checked                        */
+} ame_probit_fill_args;
+typedef struct ame_probit_score_args {
+    const float* x;        /* [S][n][d] means              (S = dims.T_local)           */
+    const float* cov;      /* [S][n][d][d] covariances                                  */
+    const float* Yt;       /* [S][n][ny][2] packed 0 / 1 network (ame_pack_y)           */
+    double* sums;          /* [S][AME_PROBIT_SUMS] fp64                                 */
+    double* work;          /* >= ame_probit_score_work_size() doubles                   */
+    uint64_t work_doubles; /* size of `work` in doubles, checked                        */
+    const uint64_t* Mt;    /* [S][n][nw] packed mask (ame_pack_mask), or NULL           */
+    int32_t mask_select;   /* 0, AME_MASK_OBSERVED or AME_MASK_HIDDEN (needs Mt)        */
+} ame_probit_score_args;
+int ame_probit_fill(const ame_dims* dims, const ame_probit_fill_args* args, void* stream);
+int ame_probit_score(const ame_dims* dims, const ame_probit_score_args* args, void* stream);
+/* Scratch doubles: 4 per tile / the feature rows of ame_predict plus 6 per tile;
+ * -1 on bad dims. */
+long long ame_probit_fill_work_size(const ame_dims* dims);
+long long ame_probit_score_work_size(const ame_dims* dims);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libame_amd.so")
 SOURCES = ("ame_sweep.hip", "ame_sweep3.hip", "ame_cov.hip", "ame_elbo.hip", "ame_capi.hip",
-           "ame_selftest.hip", "ame_align.hip", "ame_predict.hip", "ame_mstep.hip", "ame_smooth.hip", "ame_covar.hip", "ame_missing.hip", "ame_gof.hip", "ame_parts.hip")
+           "ame_selftest.hip", "ame_align.hip", "ame_predict.hip", "ame_mstep.hip", "ame_smooth.hip", "ame_covar.hip", "ame_missing.hip", "ame_gof.hip", "ame_binary.hip", "ame_parts.hip")
 # one-latent-dim diagnostic builds (-DAME_ONLY_R, tools/): no split parts, no router
 UNSPLIT_SOURCES = tuple(s for s in SOURCES if s != "ame_parts.hip")
 # Every latent dim 1..32 is compiled in; the heaviest sources are split into

@@ -610,6 +610,52 @@ int ame_simulate(const ame_dims* dims, const ame_simulate_args* a, void* stream)
     return launched(ame_simulate_dispatch(dims, a, (hipStream_t)stream), "simulate");
 }
 
+long long ame_probit_fill_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_probit_fill_work_doubles(dims);
+}
+
+int ame_probit_fill(const ame_dims* dims, const ame_probit_fill_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_probit_fill: args is NULL");
+    if (!a->x || !a->Bt || !a->Yt || !a->stat || !a->work)
+        return fail("ame_probit_fill: NULL buffer (x, Bt, Yt, stat, work)");
+    if (!(a->rho > -1.0 && a->rho < 1.0)) return fail("ame_probit_fill: rho must lie inside (-1, 1)");
+    if ((uintptr_t)a->x & 3) return fail("ame_probit_fill: x must be 4-byte aligned");
+    if (((uintptr_t)a->Bt | (uintptr_t)a->Mt | (uintptr_t)a->Yt | (uintptr_t)a->stat | (uintptr_t)a->work) & 7)
+        return fail("ame_probit_fill: Bt, Mt, Yt, stat and work must be 8-byte aligned");
+    if ((long long)a->work_doubles < ame_probit_fill_work_doubles(dims))
+        return fail("ame_probit_fill: work holds fewer doubles than ame_probit_fill_work_size");
+    if (ame_probit_fill_blocks(dims) > 0x7FFFFFFFLL)
+        return fail("ame_probit_fill: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                    dims->T_local, dims->n);
+    return launched(ame_probit_fill_dispatch(dims, a, (hipStream_t)stream), "probit_fill");
+}
+
+long long ame_probit_score_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_probit_score_work_doubles(dims);
+}
+
+int ame_probit_score(const ame_dims* dims, const ame_probit_score_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_probit_score: args is NULL");
+    if (!a->x || !a->cov || !a->Yt || !a->sums || !a->work)
+        return fail("ame_probit_score: NULL buffer (x, cov, Yt, sums, work)");
+    if (int e = check_mask_select("ame_probit_score", a->mask_select, a->Mt)) return e;
+    if (((uintptr_t)a->Yt | (uintptr_t)a->Mt | (uintptr_t)a->sums | (uintptr_t)a->work) & 7)
+        return fail("ame_probit_score: Yt, Mt, sums and work must be 8-byte aligned");
+    if ((long long)a->work_doubles < ame_probit_score_work_doubles(dims))
+        return fail("ame_probit_score: work holds fewer doubles than ame_probit_score_work_size");
+    {
+        const long long b1 = (long long)dims->T_local * dims->n, b2 = (long long)dims->T_local * ame_tri_tiles(dims->n);
+        if ((b1 > b2 ? b1 : b2) > 0x7FFFFFFFLL)
+            return fail("ame_probit_score: T_local=%d slices of n=%d exceed one launch; pass fewer slices",
+                        dims->T_local, dims->n);
+    }
+    return launched(ame_probit_score_dispatch(dims, a, (hipStream_t)stream), "probit_score");
+}
+
 long long ame_smooth_work_size(const ame_dims* dims, int nodes) {
     if (check_dims(dims)) return -1;
     if (nodes < 1 || nodes > dims->n) return fail("ame_smooth_work_size: nodes=%d outside [1, n]", nodes);

@@ -76,5 +76,12 @@ long long ame_net_moments_blocks(const ame_dims*);
 long long ame_net_triads_work_doubles(const ame_dims*);
 long long ame_net_triads_blocks(const ame_dims*);
 long long ame_simulate_blocks(const ame_dims*);
+// ame_binary.hip
+int ame_probit_fill_dispatch(const ame_dims*, const ame_probit_fill_args*, hipStream_t);
+long long ame_probit_fill_work_doubles(const ame_dims*);
+long long ame_probit_fill_blocks(const ame_dims*);
+// ame_predict.hip (MODE 3: Bernoulli scoring)
+AME_SPLIT_FN(int, ame_probit_score_dispatch, (const ame_dims*, const ame_probit_score_args*, hipStream_t))
+long long ame_probit_score_work_doubles(const ame_dims*);
 
 #undef AME_SPLIT_FN

@@ -30,11 +30,15 @@
 // K3 ame_tile_sum_kernel (ame_tile.h): fixed-order sum of a slice's tile partials.
 // MODE 2 of K2 (ame_mstep_stats): the same tiles, products and K3, with the
 //    M-step's residual second moments as the epilogue.
+// MODE 3 of K2 (ame_probit_score): the same again with a Bernoulli epilogue,
+//    pi = Phi(E[mu] / sqrt(1 + V0)) against a 0 / 1 network (C01 is not needed:
+//    its product is skipped).
 // No atomics, no spin, no O(n^2) intermediate.
 #include <type_traits>
 
 #include "ame_tile.h"
 #include "ame_internal.h"
+#include "ame_probit.h"
 
 #define AME_PKB 32       // K chunk in floats
 #define AME_PLD 34       // LDS row stride: 2 li + lq hits 32 distinct banks per half wave
@@ -248,7 +252,7 @@ ame_predict_pairs_kernel(PredictParams p) {
     product(std::integral_constant<int, 1>{}, C::oMb, C::oMa, C::MP);
     product(std::integral_constant<int, 2>{}, C::oF, C::oG, C::KVP);
     product(std::integral_constant<int, 3>{}, C::oG, C::oF, C::KVP);
-    product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
+    if (MODE != 3) product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
 
     // accumulator element (s, g) of this lane: dyad (ld.i(g), ld.j(s))
     if (MODE == 2) {   // pairs, e0^2 + V0(i,j), e1^2 + V0(j,i), e0 e1 + C01 (no noise), fp64
@@ -278,6 +282,42 @@ ame_predict_pairs_kernel(PredictParams p) {
             double* o = p.partial + ((size_t)tl * ntile + tile) * AME_MS_DYAD;
 #pragma unroll
             for (int q = 0; q < AME_MS_DYAD; ++q) o[q] = sm[q];
+        }
+        return;
+    }
+    if (MODE == 3) {   // pairs, log score, Brier, hits, ties, sum of pi over both entries, fp64
+        double sm[AME_PROBIT_SUMS];
+#pragma unroll
+        for (int q = 0; q < AME_PROBIT_SUMS; ++q) sm[q] = 0.0;
+        const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = ld.j(s);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = ld.i(g);
+                if (ame_upper_pair(i, j, n) && predict_pair_selected(p, tl, i, j)) {
+                    const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
+                    sm[0] += 1.0;
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const bool tie = (c ? y.y : y.x) > 0.5f;
+                        const double t = (double)acc[c][s][g] / sqrt(1.0 + (double)acc[2 + c][s][g]);
+                        const double pi = ame_probit_phi(t), yv = tie ? 1.0 : 0.0;
+                        sm[1] += ame_probit_logphi(tie ? t : -t);
+                        sm[2] += (yv - pi) * (yv - pi);
+                        sm[3] += ((pi > 0.5) == tie) ? 1.0 : 0.0;
+                        sm[4] += yv;
+                        sm[5] += pi;
+                    }
+                }
+            }
+        }
+        block_sum<AME_PROBIT_SUMS>(sm, red);
+        if (threadIdx.x == 0) {
+            double* o = p.partial + ((size_t)tl * ntile + tile) * AME_PROBIT_SUMS;
+#pragma unroll
+            for (int q = 0; q < AME_PROBIT_SUMS; ++q) o[q] = sm[q];
         }
         return;
     }
@@ -381,6 +421,9 @@ long long ame_predict_max_blocks(const ame_dims* dm, const ame_predict_args* a) 
 long long ame_mstep_dyad_work_doubles(const ame_dims* dm) {
     return predict_feat_doubles(dm) + (long long)dm->T_local * ame_tri_tiles(dm->n) * AME_MS_DYAD;
 }
+long long ame_probit_score_work_doubles(const ame_dims* dm) {
+    return predict_feat_doubles(dm) + (long long)dm->T_local * ame_tri_tiles(dm->n) * AME_PROBIT_SUMS;
+}
 long long ame_mstep_dyad_blocks(const ame_dims* dm) {
     const long long a = (long long)dm->T_local * dm->n, b = (long long)dm->T_local * ame_tri_tiles(dm->n);
     return a > b ? a : b;
@@ -458,6 +501,28 @@ static int launch_mstep_dyad(const ame_dims* dm, const ame_mstep_args* a, double
     hipLaunchKernelGGL(ame_tile_sum_kernel<AME_MS_DYAD>, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
                        p.ntile, a->dyad);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// MODE 3: Bernoulli scoring of a 0 / 1 network
+template <int R>
+static int launch_probit_score(const ame_dims* dm, const ame_probit_score_args* a, hipStream_t st) {
+    const int S = dm->T_local;
+    const PredictParams p = predict_common<R>(dm, a->x, a->cov, a->Yt, a->Mt, a->mask_select, a->work, st);
+    hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 3>), dim3((unsigned)((long long)S * p.ntile)),
+                       dim3(AME_NT), 0, st, p);
+    hipLaunchKernelGGL(ame_tile_sum_kernel<AME_PROBIT_SUMS>, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
+                       p.ntile, a->sums);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int AME_PFN(ame_probit_score_dispatch)(const ame_dims* dm, const ame_probit_score_args* a, hipStream_t st) {
+    switch (dm->r) {
+#define X(RR) \
+    case RR: return launch_probit_score<RR>(dm, a, st);
+        AME_FOR_EACH_R(X)
+#undef X
+        default: return -1;
+    }
 }
 
 int AME_PFN(ame_mstep_dyad_dispatch)(const ame_dims* dm, const ame_mstep_args* a, double* work,

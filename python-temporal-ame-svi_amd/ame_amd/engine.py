@@ -33,6 +33,9 @@ and t+1, so consecutive sweeps overlap and the wavefront fill is paid once per
 fit() instead of once per iteration.  Results are bit-identical to running
 the kernels in order (tests/test_gpu_parity.py::test_speculative_sweep_is_exact).
 
+On a binary model (model.set_binary) the engine owns Bt (the packed ties), a
+working network Yt beside Yt_raw and stat, and runs ame_probit_fill where the
+masked path runs ame_fill_missing (with a mask: in its place).
 With hidden dyads (model.set_missing) the engine also owns Yt_raw (the packed
 observations; Yt is then a separate working network), Mt / pairs / deg (the
 packed mask, ame_pack_mask) and corr, and runs ame_fill_missing on the main
@@ -221,7 +224,7 @@ class Constants:
         return (ctypes.c_double * 4)(*r)
 
 
-def assemble(out, n, T, d, variant, C: Constants, hidden=None, pairs_obs=None, deg_trace=None):
+def assemble(out, n, T, d, variant, C: Constants, hidden=None, pairs_obs=None, deg_trace=None, binary=None):
     """ELBO pieces and MSE from the 8 device sums (see include/ame_amd.h).
 
     Formulas: structured_mf.py:124-209 / naive_mf.py:114-191 and
@@ -235,6 +238,12 @@ def assemble(out, n, T, d, variant, C: Constants, hidden=None, pairs_obs=None, d
     deg[t][i] tr(S_it), each node's trace counted once per observed partner
     ((n - 1) out[1] when nothing is hidden).  The formulas are then the
     reference's over observed pairs.
+
+    On a binary model (``binary`` = (sum_t stat[t][1], sum_t stat[t][2]) of
+    ame_probit_fill, with ``pairs_obs`` and ``deg_trace``; ``hidden`` unused):
+    loglik = the probit bound of the observed pairs minus half the same
+    heuristic variance term, recon = the mean squared error of Phi(E[mu])
+    against the ties; none of ame_elbo's pair sums (out[0], out[7]) is read.
     """
     if pairs_obs is None:
         npairs = T * n * (n - 1) / 2.0
@@ -243,8 +252,11 @@ def assemble(out, n, T, d, variant, C: Constants, hidden=None, pairs_obs=None, d
     else:
         npairs = float(pairs_obs)
         corr = 0.0 if variant == "naive" else 0.1 * C.trRinv / d * deg_trace
-        quad, sq = out[0] - hidden[0], out[7] - hidden[1]
-    loglik = -0.5 * (npairs * (C.logdetR + 2 * LOG2PI) + quad + corr)
+        quad, sq = (0.0, binary[1]) if binary is not None else (out[0] - hidden[0], out[7] - hidden[1])
+    if binary is not None:
+        loglik = binary[0] - 0.5 * corr
+    else:
+        loglik = -0.5 * (npairs * (C.logdetR + 2 * LOG2PI) + quad + corr)
     prior0 = -0.5 * (n * (C.logdetS0 + d * LOG2PI) + out[2] + out[3])
     trans = -0.5 * (n * (T - 1) * (C.logdetQ + d * LOG2PI) + out[4] + out[5])
     ent = 0.5 * (n * T * d * (1 + LOG2PI) + out[6])
@@ -335,6 +347,17 @@ class DeviceEngine:
                 raise NotImplementedError("missing dyads together with dyadic covariates are not "
                                           "available (ame_covar_stats does not select pairs)")
             self.options = opt = replace(opt, pipeline=False, speculate=False)
+        # binary network (model.set_binary): the working network is rewritten from
+        # the new means after every sweep, as in the masked path
+        self.binary = getattr(model, "binary", None) is not None
+        if self.binary:
+            if halo is not None or self.shard.T_local != self.shard.T_total:
+                raise NotImplementedError("binary networks are not available on a time-sharded run")
+            if getattr(model, "W", None) is not None:
+                raise NotImplementedError("binary networks together with dyadic covariates are not "
+                                          "available (the residual of a 0 / 1 network has no meaning)")
+            self.options = opt = replace(opt, pipeline=False, speculate=False)
+        self.refill = self.masked or self.binary   # the working network follows the means
         self.lr = float(lr)
         self.C = Constants(model)
         sh = self.shard
@@ -426,15 +449,18 @@ class DeviceEngine:
             self._init_covariates(model)
         if self.masked:
             self._init_missing(model.missing)
+        if self.binary:
+            self._init_binary(model)
         self._mark_host_writes()
 
     # ------------------------------------------------------------------
     # missing dyads (ame_pack_mask / ame_fill_missing)
     # ------------------------------------------------------------------
-    def pack_mask(self, mask, what="mask"):
+    def pack_mask(self, mask, what="mask", symmetric=True):
         """(n, n, S) bool / uint8 mask -> (Mt [S][n][nw] int64, pairs [S] int64,
         deg [S][n] int32) on the device (ame_pack_mask); an asymmetric mask
-        raises ValueError."""
+        raises ValueError unless symmetric=False (the ties of a binary network:
+        only the words mean anything then)."""
         m = torch.as_tensor(mask)
         if m.dim() != 3 or tuple(m.shape[:2]) != (self.n, self.n) or m.shape[2] < 1:
             raise ValueError(f"{what} has shape {tuple(m.shape)}, expected ({self.n}, {self.n}, S)")
@@ -453,7 +479,7 @@ class DeviceEngine:
                                         _ptr(asym), self._sp()), "ame_pack_mask")
         bad = int(asym.item())
         del src
-        if bad:
+        if bad and symmetric:
             raise ValueError(f"{what} is not symmetric: {bad // 2} pair(s) with mask[i, j, t] != "
                              "mask[j, i, t] (the unit is the unordered pair)")
         return Mt, pairs, deg
@@ -497,6 +523,76 @@ class DeviceEngine:
         self._fill_valid = True
         self._hidden_host = None
 
+    # ------------------------------------------------------------------
+    # binary networks (ame_probit_fill / ame_probit_score)
+    # ------------------------------------------------------------------
+    def _init_binary(self, model):
+        """Pack the ties once (ame_pack_mask's layout), keep the packed 0 / 1
+        network as Yt_raw and make Yt the working network every sweep reads (a
+        copy: the diagonal and the pad column are never written again)."""
+        B = model.binary
+        if tuple(B.shape) != (self.n, self.n, self.T):
+            raise ValueError(f"B has shape {tuple(B.shape)}, expected ({self.n}, {self.n}, {self.T})")
+        self.rho = float(model.binary_rho)
+        self.Bt, _, _ = self.pack_mask(B, "B", symmetric=False)
+        with torch.cuda.device(self.dev):
+            if not self.masked:
+                self.Yt_raw = self.Yt
+                self.Yt = self.Yt_raw.clone()
+                self.Mt = None
+                self.pairs_obs = self.T * self.n * (self.n - 1) // 2
+            self.stat = torch.zeros(self.T, _lib.AME_PROBIT_STATS, dtype=torch.float64, device=self.dev)
+            ws = int(self.L.ame_probit_fill_work_size(ctypes.byref(self.dims)))
+            if ws < 0:
+                _lib.check(-1, "ame_probit_fill_work_size")
+            self.probit_work = torch.empty(ws, dtype=torch.float64, device=self.dev)
+        self.swap_consistent = False   # the two rows of a pair hold different values
+        self._fill_valid = False
+        self._hidden_host = None
+
+    def probit_fill(self):
+        """Rewrite the working network from the current means on the main stream
+        (ame_probit_fill), where the masked path runs fill_missing."""
+        a = _lib.ame_probit_fill_args(x=_ptr(self.x_a), Bt=_ptr(self.Bt),
+                                      Mt=_ptr(self.Mt) if self.Mt is not None else None, rho=self.rho,
+                                      Yt=_ptr(self.Yt), stat=_ptr(self.stat), work=_ptr(self.probit_work),
+                                      work_doubles=self.probit_work.numel())
+        tok = self._tic("probit_fill")
+        _lib.check(self.L.ame_probit_fill(ctypes.byref(self.dims), ctypes.byref(a), self._sp()),
+                   "ame_probit_fill")
+        self._toc(tok)
+        self._fill_valid = True
+        self._hidden_host = None
+
+    def _refill(self):
+        if self.binary:
+            self.probit_fill()
+        else:
+            self.fill_missing()
+
+    def probit_score(self, x, cov, Yt, Mt=None, mask_select=0):
+        """ame_probit_score over a stack of slices: per-slice sums
+        [S][AME_PROBIT_SUMS] (fp64, device) of the 0 / 1 network Yt against
+        pi = Phi(E[mu] / sqrt(1 + V0)).  Runs on the ELBO stream; the caller has
+        dropped speculation."""
+        S = int(x.shape[0])
+        n, d = self.n, self.d
+        assert tuple(x.shape) == (S, n, d) and tuple(cov.shape) == (S, n, d, d)
+        assert x.is_contiguous() and cov.is_contiguous()
+        chunk, wk = self._slice_chunk(self.L.ame_probit_score_work_size, S)
+        with torch.cuda.device(self.dev):
+            sums = torch.zeros(S, _lib.AME_PROBIT_SUMS, dtype=torch.float64, device=self.dev)
+        with self._elbo_call("probit_score") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_probit_score_args(
+                    x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]), Yt=_ptr(Yt[s0:s1]), sums=_ptr(sums[s0:s1]),
+                    work=_ptr(wk), work_doubles=wk.numel(),
+                    Mt=_ptr(Mt[s0:s1]) if Mt is not None else None, mask_select=int(mask_select))
+                _lib.check(self.L.ame_probit_score(ctypes.byref(dm), ctypes.byref(a), sp), "ame_probit_score")
+        return sums
+
     def mask_args(self, select):
         """(Yt, Mt, mask_select) for predict / mstep_stats: the packed observations
         (never the working network) with the mask and a selector, or the
@@ -504,7 +600,7 @@ class DeviceEngine:
         if not self.masked:
             if select:
                 raise ValueError("a subset needs a mask (model.set_missing)")
-            return self.Yt, None, 0
+            return (self.Yt_raw if self.binary else self.Yt), None, 0
         return self.Yt_raw, self.Mt, int(select)
 
     # ------------------------------------------------------------------
@@ -820,14 +916,14 @@ class DeviceEngine:
         if self._specs:
             done, slot = self._specs.popleft()
         else:
-            if self.masked and not self._fill_valid:   # first sweep, or after set_means
-                self.fill_missing()
+            if self.refill and not self._fill_valid:   # first sweep, or after set_means
+                self._refill()
             done, slot = self._launch_sweep()
         for ev in done:
             self.stream.wait_event(ev)
         self._commit(slot)
-        if self.masked:   # one fill serves this state's ELBO correction and the next sweep
-            self.fill_missing()
+        if self.refill:   # one fill serves this state's ELBO correction and the next sweep
+            self._refill()
         if self.halo is not None:
             self.halo.after_sweep(self)
 
@@ -864,8 +960,8 @@ class DeviceEngine:
         which writes no sums."""
         if not pairs_only and not self._cov_terms_valid:
             self.refresh_cov_terms()
-        if self.masked and not self._fill_valid:
-            self.fill_missing()
+        if self.refill and not self._fill_valid:
+            self._refill()
         prev_final = None
         if self.halo is not None and not pairs_only:
             prev_final = self.halo.prev_final(self)
@@ -903,6 +999,24 @@ class DeviceEngine:
 
     def terms(self, speculate=0):
         out = self.sums(speculate)
+        if self.binary:
+            if self._hidden_host is None:
+                # the bound and the Brier sum, slice by slice in time order, and each
+                # node's trace once per observed partner
+                rows = self.stat.cpu().tolist()
+                bound = brier = 0.0
+                for row in rows:
+                    bound += row[1]
+                    brier += row[2]
+                if self.masked:
+                    tr = self.cov_terms.view(self.T, self.n, 4)[:, :, 1]
+                    deg_trace = float((self._deg64 * tr).sum().item())
+                else:
+                    deg_trace = (self.n - 1) * out[1]
+                self._hidden_host = ((bound, brier), deg_trace)
+            bin_sums, deg_trace = self._hidden_host
+            return assemble(out, self.n, self.T, self.d, self.variant, self.C, pairs_obs=self.pairs_obs,
+                            deg_trace=deg_trace, binary=bin_sums)
         if not self.masked:
             return assemble(out, self.n, self.T, self.d, self.variant, self.C)
         if self._hidden_host is None:

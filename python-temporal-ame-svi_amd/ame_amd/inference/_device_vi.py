@@ -300,6 +300,48 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         eng.discard_speculation()
         return eng
 
+    # ---------------- binary networks (extension, model.set_binary) ----------------
+    def _binary(self) -> bool:
+        return getattr(self.model, "binary", None) is not None
+
+    def _refuse_binary(self, what, why):
+        if self._binary():
+            raise NotImplementedError(f"{what} is not available on a binary model (model.set_binary): {why}")
+
+    def _binary_check(self, subset) -> dict:
+        """predictive_check of a binary model: Bernoulli scores of the ties under
+        pi = Phi(E[mu] / sqrt(1 + V0)), the exact marginal P(y = 1) under q."""
+        select = self._subset(subset)
+        eng = self._predict_engine()
+        Yt, Mt, select = eng.mask_args(select)
+        s = eng.probit_score(eng.x_a, eng.cov, Yt, Mt=Mt, mask_select=select)
+        s = s.detach().to("cpu", torch.float64).numpy()
+        pairs = s[:, 0].copy()
+        ent = 2.0 * pairs
+        return {"pairs": pairs, "log_score": s[:, 1].copy(), "brier": s[:, 2] / ent,
+                "accuracy": s[:, 3] / ent, "base_rate": s[:, 4] / ent, "mean_prob": s[:, 5] / ent}
+
+    def predict_proba(self, times, rows=None, cols=None, max_elements=2 ** 27) -> torch.Tensor:
+        """P(y_ij = 1) of a binary model for a block, (ni, nj, S, 2) fp32 on the
+        CPU in Y's (ij, ji) layout: pi = Phi(E[mu] / sqrt(1 + V0)) from
+        predict_dyads' moments of the mean, formed on the device.  The diagonal
+        is NaN.  ``times`` is an int or a slice, ``rows`` / ``cols`` contiguous
+        ranges or slices."""
+        if not self._binary():
+            raise ValueError("predict_proba needs a binary model (model.set_binary)")
+        eng = self._predict_engine()
+        t0, t1 = self._range(times, self.T, "times")
+        i0, i1 = self._range(rows, self.n, "rows")
+        j0, j1 = self._range(cols, self.n, "cols")
+        count = (t1 - t0) * (i1 - i0) * (j1 - j0) * 5
+        if count > int(max_elements):
+            raise ValueError(f"{count} device floats exceed max_elements={int(max_elements)}; "
+                             "ask for fewer times, rows or columns")
+        _, dense = eng.predict(eng.x_a[t0:t1], eng.cov[t0:t1], include_noise=False, block=(i0, i1, j0, j1))
+        dd = dense.double()
+        pi = 0.5 * torch.erfc(-(dd[..., 0:2] / torch.sqrt(1.0 + dd[..., 2:4])) * math.sqrt(0.5))
+        return pi.float().permute(1, 2, 0, 3).to("cpu").contiguous()
+
     # ---------------- exact smoothing across time (extension) ----------------
     def smooth(self, partners=None) -> SmoothResult:
         """Each node's exact Gaussian posterior over its whole trajectory given
@@ -312,6 +354,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         only, so its covariances widen with the number of hidden partners."""
         if partners not in (None, "observed"):
             raise ValueError(f'partners must be None or "observed" (got {partners!r})')
+        self._refuse_binary("smooth / smoothed=", "the smoother conditions on Gaussian observations")
         if self._time_sharded():
             raise NotImplementedError("smooth is not available on a time-sharded run: the forward "
                                       "pass would have to carry (J_t^-1, g_t) across ranks")
@@ -375,7 +418,16 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         returns all T steps.  With hidden dyads (model.set_missing) ``subset`` chooses the
         pairs: "observed" (the default) scores the pairs the fit has seen,
         "held_out" the hidden ones against ``model.Y``, out of sample; ``pairs``
-        counts the chosen ones."""
+        counts the chosen ones.
+        On a binary model (model.set_binary) the scores are Bernoulli: fp64 arrays
+        of length T ``pairs``, ``log_score`` (sum over both entries of the chosen
+        pairs of log P(y_ij)), and per entry ``brier``, ``accuracy`` (share with
+        (pi > 1/2) == y), ``base_rate`` (share of ties) and ``mean_prob``, with
+        pi = Phi(E[mu] / sqrt(1 + V0)); levels / include_noise are not used."""
+        if self._binary():
+            if smoothed:
+                self._refuse_binary("smoothed=", "the smoother conditions on Gaussian observations")
+            return self._binary_check(subset)
         levels, zsq, csq = self._thresholds(levels)
         select = self._subset(subset)
         eng, x, cov, _ = self._state(smoothed)
@@ -468,6 +520,8 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         ``missing_future`` (n, n, h), bool or uint8 and symmetric as in
         model.set_missing: only the observed future pairs are scored."""
         levels, zsq, csq = self._thresholds(levels)
+        self._refuse_binary("forecast_check", "it scores Gaussian observations; forecast() and "
+                            "predict_proba() give the states and the in-sample probabilities")
         Y_future = torch.as_tensor(Y_future)
         Wf = self._future_covariates(W_future, Y_future.shape[2] if Y_future.dim() == 4 else 1)
         if Wf is not None:
@@ -518,6 +572,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         its means and marginals in place of the fit's, and its lag-one
         cross-covariances added into A10."""
         from .. import mstep
+        self._refuse_binary("fit_em / m_step", "no M-step is defined for probit data (rho is fixed)")
         if smoothed:
             eng, x, cov, sm = self._state(smoothed)
             state, dyad = eng.mstep_stats(x, cov)
@@ -565,6 +620,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         (fp32) and rebuilds the engine's residual network.  A singular system
         for beta raises ValueError and applies nothing."""
         from .. import mstep
+        self._refuse_binary("fit_em / m_step", "no M-step is defined for probit data (rho is fixed)")
         update = tuple(update)
         if "beta" in update and getattr(self.model, "W", None) is None:
             raise ValueError('update has "beta" but the model has no covariates (set_covariates)')
@@ -602,6 +658,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         make them.  smoothed=True: every M-step uses the statistics of the
         smoothed posterior; F and the closed forms are the same (F is linear in
         the statistics)."""
+        self._refuse_binary("fit_em / m_step", "no M-step is defined for probit data (rho is fixed)")
         if smoothed and self._time_sharded():
             raise NotImplementedError("smoothed=True is not available on a time-sharded run")
         masked = getattr(self.model, "missing", None) is not None
@@ -625,6 +682,7 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
     def _gof_engine(self):
         """The engine, after the refusals of the goodness-of-fit calls (raised
         before anything is launched for them)."""
+        self._refuse_binary("gof / network_statistics", "the simulated networks would be Gaussian")
         if self._time_sharded():
             raise NotImplementedError("network statistics are not available on a time-sharded run: "
                                       "every rank would simulate and reduce its own slices only")

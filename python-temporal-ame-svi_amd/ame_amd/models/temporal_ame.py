@@ -109,6 +109,40 @@ class TemporalAMEModel:
         self.beta: Optional[torch.Tensor] = None
         # hidden dyads (extension, set_missing): none by default
         self.missing: Optional[torch.Tensor] = None
+        # binary network with a probit link (extension, set_binary): none by default
+        self.binary: Optional[torch.Tensor] = None
+        self.binary_rho: Optional[float] = None
+
+    def set_binary(self, B, rho: float = 0.0) -> None:
+        """Fit a binary network with a probit link (the reference is Gaussian
+        only).  ``B`` is (n, n, T), bool or uint8, B[i, j, t] = the tie i -> j; it
+        need not be symmetric and the diagonal is ignored.  The model is
+        z_pair ~ N(mu_pair, [[1, rho], [rho, 1]]), y = 1[z > 0] (the noise scale is
+        not identified), so ``R`` / ``R_inv`` become that matrix, ``Y`` the fp32
+        0 / 1 network in the (B_ij, B_ji) layout and ``binary`` the bool ties.
+        ``None`` clears ``binary`` (Y, R and R_inv stay as they are).  Set it
+        before a VI object is built on the model, like set_missing."""
+        if B is None:
+            self.binary = None
+            self.binary_rho = None
+            return
+        b = torch.as_tensor(B)
+        if b.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"B has dtype {b.dtype}, expected bool or uint8")
+        if tuple(b.shape) != (self.n, self.n, self.T):
+            raise ValueError(f"B has shape {tuple(b.shape)}, expected ({self.n}, {self.n}, {self.T})")
+        rho = float(rho)
+        if not -1.0 < rho < 1.0:
+            raise ValueError(f"rho={rho} outside (-1, 1)")
+        b = (b != 0).detach().to("cpu").clone()
+        idx = torch.arange(self.n)
+        b[idx, idx] = False
+        self.binary = b.contiguous()
+        self.binary_rho = rho
+        self.R = torch.tensor([[1.0, rho], [rho, 1.0]], dtype=torch.float32)
+        self.R_inv = torch.linalg.inv(self.R)
+        f = b.to(torch.float32)
+        self.Y = torch.stack([f, f.transpose(0, 1)], dim=-1).contiguous()
 
     def set_missing(self, mask) -> None:
         """Mark dyads as unobserved (the reference has no such notion).  ``mask``
