@@ -24,6 +24,11 @@ Bounds.
   whose pi lies within 1e-6 of 1/2 (at most 0.1 % of them, checked on the
   reference); the three sums within 5e-6 x the sum of |summand|.
   End to end: within 4 x the oracle's own fp32-vs-fp64 deviation (test_gpu_missing.py's rule).
+  The tails (section 5): on probit_ref.grid_case the device forms every pair mean
+  exactly, so both kernels are held to 4 x TAIL_TAU0 = 1.44e-14 x the sum of
+  |terms| of an mpmath fixture, TAIL_TAU0 being the scipy reference's own
+  deviation from it; the device measures at most 0.20 of that.  The random
+  states run once more with every third pair's ties against their means.
 """
 import ctypes
 import functools
@@ -63,21 +68,22 @@ def _i32(a):
 
 class _Device:
     """make_state's means and covariances and ties drawn from them, on the device
-    in the layouts of include/ame_amd.h, with raw C-ABI calls over slice ranges."""
+    in the layouts of include/ame_amd.h, with raw C-ABI calls over slice ranges.
+    ties "drawn": 1[mu + N(0, 1) > 0], which almost always agrees with the mean;
+    "against": the same draw with both ties of every third pair i < j (in row
+    order) set against their means.  `state` = (X, S, B) replaces all three."""
 
-    def __init__(self, case):
+    def __init__(self, case, ties="drawn", state=None):
         import torch
         from ame_amd import _lib
         self.torch, self.L, self.lib = torch, _lib, _lib.lib()
         n, T, r = self.case = case
         self.dev = torch.device("cuda", 0)
-        self.X, self.S = PR.make_state(n, T, r)
-        X64 = self.X.astype(np.float64)
-        rng = np.random.default_rng(100 + n + 7 * T + r)
-        # ties from the means plus unit noise, each direction on its own: B is not symmetric
-        mu = np.stack([MR.mean_mu(X64[:, t], r)[:, :, 0] for t in range(T)], 2)
-        self.B = (mu + rng.standard_normal(mu.shape)) > 0
-        self.B[np.arange(n), np.arange(n)] = False
+        if state is not None:
+            self.X, self.S, self.B = state
+        else:
+            self.X, self.S = PR.make_state(n, T, r)
+            self.B = BR.state_ties(self.X, case, ties)
         self.x = torch.from_numpy(self.X).permute(1, 0, 2).contiguous().to(self.dev)
         self.cov = torch.from_numpy(self.S).permute(1, 0, 2, 3).contiguous().to(self.dev)
         dims = self.dims(0, T)
@@ -183,8 +189,8 @@ class _Device:
 
 
 @functools.lru_cache(maxsize=None)
-def _device(case):
-    return _Device(case)
+def _device(case, ties="drawn"):
+    return _Device(case, ties)
 
 
 # ---------------------------------------------------------------------------
@@ -192,8 +198,17 @@ def _device(case):
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("case", CASES + EVERY_R, ids=IDS)
 def test_fill_writes_every_pair_within_the_bound(case, gpu_device):
-    dv = _device(case)
-    n, T, r = case
+    _check_fill_writes(_device(case))
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_fill_writes_every_pair_within_the_bound_with_ties_against_the_means(case, gpu_device):
+    """s m reaches about -23 at r = 16, 32 with p != 0; the derived bound holds for any ties."""
+    _check_fill_writes(_device(case, "against"))
+
+
+def _check_fill_writes(dv):
+    n, T, r = case = dv.case
     X64 = dv.X.astype(np.float64)
     U, V = np.abs(X64[:, :, 2:2 + r]), np.abs(X64[:, :, 2 + r:])
     eye = np.eye(n, dtype=bool)
@@ -299,8 +314,16 @@ def _assert_score_rows(got, want, mag, near, tag):
 
 @pytest.mark.parametrize("case", CASES + EVERY_R, ids=IDS)
 def test_score_sums(case, gpu_device):
-    dv = _device(case)
-    n, T, r = case
+    _check_score_sums(_device(case))
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_score_sums_with_ties_against_the_means(case, gpu_device):
+    _check_score_sums(_device(case, "against"))
+
+
+def _check_score_sums(dv):
+    n, T, r = case = dv.case
     plain = dv.score()
     want, mag, near = BR.score_rows(dv.X, dv.S, r, dv.B)
     assert (plain[:, 0] == n * (n - 1) // 2).all()
@@ -534,3 +557,116 @@ def test_unsupported_combinations_say_which(gpu_device):
     assert (chk["pairs"] == n * (n - 1) // 2).all()
     with pytest.raises(ValueError):
         vi.predictive_check(subset="held_out")
+
+
+# ---------------------------------------------------------------------------
+# 5. the tails: exact pair means against the mpmath fixture
+# ---------------------------------------------------------------------------
+# probit_ref.grid_case: r = 1, u = v = 0 and a, b on a 2^-10 grid, so the device
+# forms every pair mean exactly (fp64 adds in the fill kernel, fp32 MFMA in the
+# score kernel) and everything after it is fp64: held to 4 x TAIL_TAU0 of
+# tests/golden/probit_tails.npz (mpmath), TAIL_TAU0 = 3.6e-15 being the scipy
+# reference's own deviation from it.  One slice per regime of s m, so the worst
+# ratio names the function and the argument range.
+TAIL_TOL = 4.0 * BR.TAIL_TAU0
+
+
+@functools.lru_cache(maxsize=None)
+def _tails():
+    from conftest import golden
+    fx = golden("probit_tails.npz")
+    return {k: fx[k] for k in fx.files}
+
+
+@functools.lru_cache(maxsize=None)
+def _grid_device(n, cov):
+    g = BR.grid_case(n, 0.0)
+    return _Device((n, g["T"], g["r"]), state=(g["X"], g["S"][cov], g["B"]))
+
+
+@pytest.mark.parametrize("n", BR.GRID_SHAPES, ids=lambda n: f"n{n}")
+def test_fill_on_the_tail_grid(n, gpu_device):
+    """stat[0] exact, stat[1..3] within 4 x TAIL_TAU0 x the sum of |elementary
+    term| of the fixture; every observed entry within 2^-24 |value| + 2^-40 (1 +
+    |d|) of own mean + d (the one fp32 rounding the kernel promises, plus slack for
+    d's last bits; d from the fixture at n = 20, from the scipy reference at 65).
+    Measured on an MI355X, worst |stat - fixture| / (4 TAIL_TAU0 sum|terms|) per
+    slice 0..5 over both shapes, both masks and the five rho: 0.022, 0.015, 0.011,
+    0.190, 0.011, 0.029; entries at most 0.999 of their bound."""
+    fx, dv = _tails(), _grid_device(n, "unit")
+    g = BR.grid_case(n, 0.0)
+    T = g["T"]
+    X64 = g["X"].astype(np.float64)
+    # (T, n, n, 2): row i holds (a_i, b_i), its own-perspective mean with p = q = 0
+    own = np.stack([X64[:, :, 0].T[:, :, None].repeat(n, 2), X64[:, :, 1].T[:, :, None].repeat(n, 2)], -1)
+    eye = np.eye(n, dtype=bool)
+    worst = np.zeros(T)
+    for rho in BR.GRID_RHOS:
+        if n == BR.GRID_SHAPES[0]:
+            d = fx[BR.grid_key(n, rho, "d")].transpose(2, 0, 1, 3)
+        else:
+            d = np.stack([BR.corrections(X64[:, t], g["B"][:, :, t], rho, 1)[1] for t in range(T)])
+        for name in BR.GRID_MASKS:
+            mask = g["masks"][name]
+            Mt = dv.packed(name)
+            got, stat = dv.fill(rho, Mt)
+            tag = f"n{n} {name} rho={rho}"
+            want, mag = fx[BR.grid_key(n, rho, "stat", name)], fx[BR.grid_key(n, rho, "statmag", name)]
+            assert np.isnan(got[:, :, :n][:, eye]).all() and np.isnan(got[:, :, n:]).all(), tag
+            assert np.isfinite(got[:, :, :n][:, ~eye]).all() and np.isfinite(stat).all(), tag
+            assert np.array_equal(stat[:, 0], want[:, 0]), tag
+            ratio = np.abs(stat - want)[:, 1:] / (TAIL_TOL * mag[:, 1:])
+            print(f"{tag}: |stat - fixture| / allowance per slice {ratio.max(1).tolist()}")
+            worst = np.maximum(worst, ratio.max(1))
+            assert (ratio <= 1.0).all(), (tag, ratio.tolist())
+            obs = ~eye[None] & (~MR.clean(mask).transpose(2, 0, 1) if mask is not None else True)
+            value = own + d
+            err = np.abs(got[:, :, :n].astype(np.float64) - value)
+            bound = 2.0 ** -24 * np.abs(value) + 2.0 ** -40 * (1.0 + np.abs(d))
+            r_e = (err / bound)[np.broadcast_to(obs, err.shape[:3])]
+            print(f"{tag}: observed entries, max err / bound = {r_e.max():.3f}")
+            assert (r_e <= 1.0).all(), (tag, float(r_e.max()))
+            if mask is not None:
+                hid = MR.clean(mask).transpose(2, 0, 1)
+                assert np.array_equal(got[:, :, :n][hid], own.astype(np.float32)[hid]), tag
+            # the same bits from a second call and from every two-way split of the slices
+            got2, stat2 = dv.fill(rho, Mt)
+            assert np.array_equal(stat2.view(np.uint64), stat.view(np.uint64)), tag
+            assert np.array_equal(_i32(got2), _i32(got)), tag
+            for k in range(1, T):
+                ga, sa = dv.fill(rho, Mt, 0, k)
+                gb, sb = dv.fill(rho, Mt, k, T)
+                assert np.array_equal(np.concatenate([sa, sb]).view(np.uint64), stat.view(np.uint64)), (tag, k)
+                assert np.array_equal(_i32(np.concatenate([ga, gb])), _i32(got)), (tag, k)
+    print(f"n{n}: worst |stat - fixture| / (4 tau0 sum|terms|) per slice {[f'{w:.3f}' for w in worst]}")
+
+
+@pytest.mark.parametrize("cov", BR.GRID_COVS)
+@pytest.mark.parametrize("n", BR.GRID_SHAPES, ids=lambda n: f"n{n}")
+def test_score_on_the_tail_grid(n, cov, gpu_device):
+    """Pairs, ties and hits exact (no pi lies near 1/2: |t| >= 2^-11); the sums
+    [1], [2], [5] within 4 x TAIL_TAU0 x the sum of |summand| of the fixture, over
+    every pair and over the observed and the hidden pairs of a 30 % mask, with
+    t = m ("unit") and t = m or m / 2 by the row node ("scaled").  Measured on an
+    MI355X, worst |sums - fixture| / (4 TAIL_TAU0 sum|summand|) per slice 0..5:
+    unit 0.022, 0.015, 0.010, 0.202, 0.015, 0.013; scaled 0.020, 0.013, 0.015,
+    0.050, 0.015, 0.013."""
+    fx, dv = _tails(), _grid_device(n, cov)
+    T = BR.GRID_T
+    Mt = dv.packed("random30")
+    worst = np.zeros(T)
+    for sel in BR.GRID_SELECTS:
+        got = dv.score(Mt if sel else None, sel)
+        want, mag = fx[BR.grid_key(n, None, "score", cov, sel)], fx[BR.grid_key(n, None, "scoremag", cov, sel)]
+        tag = f"n{n} {cov} select {sel}"
+        assert np.isfinite(got).all(), tag
+        assert np.array_equal(got[:, [0, 3, 4]], want[:, [0, 3, 4]]), (tag, got, want)
+        ratio = np.abs(got - want)[:, [1, 2, 5]] / (TAIL_TOL * mag[:, [1, 2, 5]])
+        print(f"{tag}: |sums - fixture| / allowance per slice {ratio.max(1).tolist()}")
+        worst = np.maximum(worst, ratio.max(1))
+        assert (ratio <= 1.0).all(), (tag, ratio.tolist())
+        assert np.array_equal(dv.score(Mt if sel else None, sel).view(np.uint64), got.view(np.uint64)), tag
+        for k in range(1, T):
+            both = np.concatenate([dv.score(Mt if sel else None, sel, 0, k), dv.score(Mt if sel else None, sel, k, T)])
+            assert np.array_equal(both.view(np.uint64), got.view(np.uint64)), (tag, k)
+    print(f"n{n} {cov}: worst |sums - fixture| / (4 tau0 sum|summand|) per slice {[f'{w:.3f}' for w in worst]}")
