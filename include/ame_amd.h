@@ -49,6 +49,9 @@
  *   ame_probit_fill,  replace nothing in the reference: binary networks with a
  *   ame_probit_score  probit link (the working network the sweep reads in place of
  *                     a 0 / 1 network; Bernoulli scores of held-out links).
+ *   ame_probit_rank,  replace nothing in the reference: ranking the links of a binary
+ *   ame_probit_select network (per-slice class histograms of the scores for ROC / AUC;
+ *                     the records of the highest-scoring entries for a top-k list).
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -743,6 +746,79 @@ int ame_probit_score(const ame_dims* dims, const ame_probit_score_args* args, vo
  * -1 on bad dims. */
 long long ame_probit_fill_work_size(const ame_dims* dims);
 long long ame_probit_score_work_size(const ame_dims* dims);
+
+/* ---- binary networks: ranking links (ROC / AUC histograms, top-k selection) -----------
+ * Replaces nothing the reference computes.  The score of a directed entry is
+ *   t = E[mu] / sqrt(1 + V0),
+ * the fp64 quantity ame_probit_score forms (pi = Phi(t) is monotone in it, and t keeps
+ * its resolution where pi rounds to 0 or 1); class 1 is a tie (Yt > 1/2 of a 0 / 1
+ * network).  Pairs i < j are selected by Mt / mask_select exactly as in
+ * ame_probit_score, and both entries of a selected pair are taken: entry 0 of pair
+ * (i, j) is i -> j, entry 1 is j -> i.  The bin of an entry is, in fp64,
+ *   b = floor((t + t_max) * scale)   clamped to [0, nbins - 1]   (a NaN t: bin 0),
+ * an add, then a multiply (nothing a compiler can contract), with scale = nbins /
+ * (2 t_max) computed once by the caller in fp64 and passed in: a host reference given
+ * the same t gets the same bin.
+ *
+ * ame_probit_rank: hist[s][c][b] = entries of slice s and class c in bin b, uint64.
+ * The call zeroes hist on its stream, every workgroup (one per slice and 64 x 64 tile)
+ * counts its tile into a uint32 [2][nbins] histogram in LDS with LDS integer atomics
+ * and adds the non-zero bins to hist with global 64-bit integer atomics.  Integer adds
+ * do not depend on their order: the same bits from run to run, for any split of the
+ * slices over calls and for both slice mappings.
+ *
+ * ame_probit_select: the same pass; every selected entry with b >= bin_min[s], and,
+ * when tie_filter is 0 or 1, of that class (-1: both), becomes a record in slice s's
+ * region records[offset[s] .. offset[s + 1]).  count[s] (zeroed by the call on its
+ * stream) receives the number of entries that passed; one beyond the region's capacity
+ * is counted and not written, so count[s] > offset[s + 1] - offset[s] tells the caller.
+ * A workgroup reserves its run of the region with one global integer atomic, so the
+ * order of the records inside a region is free; their content is not.  slice0 is added
+ * to the slice index a record carries (a caller that passes its slices in chunks).
+ * No floating-point atomics anywhere. */
+#define AME_RANK_MAX_BINS 2048
+typedef struct ame_probit_rank_args {
+    const float* x;        /* [S][n][d] means              (S = dims.T_local)           */
+    const float* cov;      /* [S][n][d][d] covariances                                  */
+    const float* Yt;       /* [S][n][ny][2] packed 0 / 1 network (ame_pack_y)           */
+    uint64_t* hist;        /* [S][2][nbins] uint64, overwritten                         */
+    double* work;          /* >= ame_probit_rank_work_size() doubles                    */
+    uint64_t work_doubles; /* size of `work` in doubles, checked                        */
+    const uint64_t* Mt;    /* [S][n][nw] packed mask (ame_pack_mask), or NULL           */
+    int32_t mask_select;   /* 0, AME_MASK_OBSERVED or AME_MASK_HIDDEN (needs Mt)        */
+    int32_t nbins;         /* 1 .. AME_RANK_MAX_BINS                                    */
+    double t_max;          /* > 0: the bins cover [-t_max, t_max), the end bins the rest */
+    double scale;          /* nbins / (2 t_max) in fp64                                 */
+} ame_probit_rank_args;
+typedef struct ame_link_record {
+    double t;              /* the score                                                 */
+    int32_t slice;         /* slice0 + the slice's index in the call                    */
+    int32_t sender, receiver;
+    int32_t tie;           /* 0 / 1: the entry's class                                  */
+} ame_link_record;
+typedef struct ame_probit_select_args {
+    const float* x;        /* as ame_probit_rank_args                                   */
+    const float* cov;
+    const float* Yt;
+    double* work;          /* >= ame_probit_select_work_size() doubles                  */
+    uint64_t work_doubles;
+    const uint64_t* Mt;
+    int32_t mask_select;
+    int32_t nbins;
+    double t_max;
+    double scale;
+    const int32_t* bin_min; /* [S] smallest bin taken                                   */
+    int32_t tie_filter;    /* -1: both classes; 0 / 1: that class only                  */
+    int32_t slice0;        /* added to the slice index of a record                      */
+    const int64_t* offset; /* [S + 1] non-decreasing record offsets of the regions      */
+    uint64_t* count;       /* [S] entries that passed, overwritten                      */
+    ame_link_record* records; /* offset[S] records                                      */
+} ame_probit_select_args;
+int ame_probit_rank(const ame_dims* dims, const ame_probit_rank_args* args, void* stream);
+int ame_probit_select(const ame_dims* dims, const ame_probit_select_args* args, void* stream);
+/* Scratch doubles: the feature rows of ame_predict; -1 on bad dims. */
+long long ame_probit_rank_work_size(const ame_dims* dims);
+long long ame_probit_select_work_size(const ame_dims* dims);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

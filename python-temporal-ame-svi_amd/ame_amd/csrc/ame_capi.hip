@@ -656,6 +656,65 @@ int ame_probit_score(const ame_dims* dims, const ame_probit_score_args* a, void*
     return launched(ame_probit_score_dispatch(dims, a, (hipStream_t)stream), "probit_score");
 }
 
+long long ame_probit_rank_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_probit_rank_work_doubles(dims);
+}
+
+long long ame_probit_select_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_probit_rank_work_doubles(dims);
+}
+
+// what ame_probit_rank and ame_probit_select share: the bin rule and the launch size
+static int check_rank_common(const char* who, const ame_dims* dims, int nbins, double t_max, double scale,
+                             unsigned long long work_doubles) {
+    const long long b1 = (long long)dims->T_local * dims->n, b2 = (long long)dims->T_local * ame_tri_tiles(dims->n);
+    if (nbins < 1 || nbins > AME_RANK_MAX_BINS)
+        snprintf(g_err, sizeof(g_err), "%s: nbins=%d outside [1, %d]", who, nbins, AME_RANK_MAX_BINS);
+    else if (!(t_max > 0.0) || !(t_max < 1e300))
+        snprintf(g_err, sizeof(g_err), "%s: t_max must be positive and finite", who);
+    else if (!(scale > 0.0) || !(scale < 1e300))
+        snprintf(g_err, sizeof(g_err), "%s: scale must be positive and finite", who);
+    else if ((long long)work_doubles < ame_probit_rank_work_doubles(dims))
+        snprintf(g_err, sizeof(g_err), "%s: work holds fewer doubles than %s_work_size", who, who);
+    else if ((b1 > b2 ? b1 : b2) > 0x7FFFFFFFLL)
+        snprintf(g_err, sizeof(g_err), "%s: T_local=%d slices of n=%d exceed one launch; pass fewer slices", who,
+                 dims->T_local, dims->n);
+    else
+        return 0;
+    return -1;
+}
+
+int ame_probit_rank(const ame_dims* dims, const ame_probit_rank_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_probit_rank: args is NULL");
+    if (!a->x || !a->cov || !a->Yt || !a->hist || !a->work)
+        return fail("ame_probit_rank: NULL buffer (x, cov, Yt, hist, work)");
+    if (int e = check_mask_select("ame_probit_rank", a->mask_select, a->Mt)) return e;
+    if (((uintptr_t)a->Yt | (uintptr_t)a->Mt | (uintptr_t)a->hist | (uintptr_t)a->work) & 7)
+        return fail("ame_probit_rank: Yt, Mt, hist and work must be 8-byte aligned");
+    if (int e = check_rank_common("ame_probit_rank", dims, a->nbins, a->t_max, a->scale, a->work_doubles)) return e;
+    return launched(ame_probit_rank_dispatch(dims, a, (hipStream_t)stream), "probit_rank");
+}
+
+int ame_probit_select(const ame_dims* dims, const ame_probit_select_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_probit_select: args is NULL");
+    if (!a->x || !a->cov || !a->Yt || !a->work || !a->bin_min || !a->offset || !a->count || !a->records)
+        return fail("ame_probit_select: NULL buffer (x, cov, Yt, work, bin_min, offset, count, records)");
+    if (int e = check_mask_select("ame_probit_select", a->mask_select, a->Mt)) return e;
+    if (((uintptr_t)a->Yt | (uintptr_t)a->Mt | (uintptr_t)a->work | (uintptr_t)a->offset | (uintptr_t)a->count |
+         (uintptr_t)a->records) & 7)
+        return fail("ame_probit_select: Yt, Mt, work, offset, count and records must be 8-byte aligned");
+    if ((uintptr_t)a->bin_min & 3) return fail("ame_probit_select: bin_min must be 4-byte aligned");
+    if (a->tie_filter < -1 || a->tie_filter > 1)
+        return fail("ame_probit_select: tie_filter=%d, expected -1, 0 or 1", a->tie_filter);
+    if (int e = check_rank_common("ame_probit_select", dims, a->nbins, a->t_max, a->scale, a->work_doubles))
+        return e;
+    return launched(ame_probit_select_dispatch(dims, a, (hipStream_t)stream), "probit_select");
+}
+
 long long ame_smooth_work_size(const ame_dims* dims, int nodes) {
     if (check_dims(dims)) return -1;
     if (nodes < 1 || nodes > dims->n) return fail("ame_smooth_work_size: nodes=%d outside [1, n]", nodes);

@@ -83,5 +83,9 @@ long long ame_probit_fill_blocks(const ame_dims*);
 // ame_predict.hip (MODE 3: Bernoulli scoring)
 AME_SPLIT_FN(int, ame_probit_score_dispatch, (const ame_dims*, const ame_probit_score_args*, hipStream_t))
 long long ame_probit_score_work_doubles(const ame_dims*);
+// ame_predict.hip (MODE 4, 5: score histograms and top-scoring records)
+AME_SPLIT_FN(int, ame_probit_rank_dispatch, (const ame_dims*, const ame_probit_rank_args*, hipStream_t))
+AME_SPLIT_FN(int, ame_probit_select_dispatch, (const ame_dims*, const ame_probit_select_args*, hipStream_t))
+long long ame_probit_rank_work_doubles(const ame_dims*);
 
 #undef AME_SPLIT_FN

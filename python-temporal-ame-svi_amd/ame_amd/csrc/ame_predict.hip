@@ -33,7 +33,15 @@
 // MODE 3 of K2 (ame_probit_score): the same again with a Bernoulli epilogue,
 //    pi = Phi(E[mu] / sqrt(1 + V0)) against a 0 / 1 network (C01 is not needed:
 //    its product is skipped).
-// No atomics, no spin, no O(n^2) intermediate.
+// MODE 4 of K2 (ame_probit_rank): MODE 3's products; the epilogue bins the score
+//    t = E[mu] / sqrt(1 + V0) of both entries into a per-workgroup uint32
+//    [2][nbins] histogram in LDS (LDS integer atomics) and adds its non-zero
+//    bins to the slice's uint64 histogram with global integer atomics.
+// MODE 5 of K2 (ame_probit_select): the same pass; entries at or above the
+//    slice's threshold bin are appended to the slice's region of records (one
+//    global integer atomic per workgroup reserves its run).
+// Modes 0 - 3: no atomics, no spin, no O(n^2) intermediate.  Modes 4, 5: integer
+// atomics only (order-independent sums / a free order the host sorts away).
 #include <type_traits>
 
 #include "ame_tile.h"
@@ -72,6 +80,14 @@ struct PredictParams {
     float* dense;
     const unsigned long long* Mt;   // [S][n][nw] packed mask, or nullptr
     int nw, mask_select;            // 0: every pair i < j; AME_MASK_OBSERVED / AME_MASK_HIDDEN
+    // MODE 4, 5: the bin rule; MODE 4: hist [S][2][nbins]; MODE 5: the selection
+    int nbins, tie_filter, slice0;
+    double t_max, scale;
+    unsigned long long* hist;
+    const int* bin_min;             // [S]
+    const long long* offset;        // [S + 1] record offsets of the slices' regions
+    unsigned long long* count;      // [S] entries that passed (also those beyond a region)
+    ame_link_record* rec;
 };
 
 // whether pair (i, j), i < j < n, of slice tl is selected (MODE 0 scoring, MODE 2 statistics)
@@ -80,6 +96,13 @@ __device__ __forceinline__ bool predict_pair_selected(const PredictParams& p, in
     const unsigned long long wd = p.Mt[((size_t)tl * p.n + i) * p.nw + (j >> 6)];
     const bool hidden = (wd >> (j & 63)) & 1ull;
     return hidden == (p.mask_select == AME_MASK_HIDDEN);
+}
+
+// the histogram bin of a score (include/ame_amd.h): an add, then a multiply, then
+// floor, clamped to [0, nbins - 1]; a NaN score goes to bin 0
+__device__ __forceinline__ int predict_rank_bin(const PredictParams& p, double t) {
+    const double fb = floor((t + p.t_max) * p.scale);
+    return !(fb >= 0.0) ? 0 : (fb > (double)(p.nbins - 1) ? p.nbins - 1 : (int)fb);
 }
 
 // ---------------------------------------------------------------------------
@@ -252,7 +275,7 @@ ame_predict_pairs_kernel(PredictParams p) {
     product(std::integral_constant<int, 1>{}, C::oMb, C::oMa, C::MP);
     product(std::integral_constant<int, 2>{}, C::oF, C::oG, C::KVP);
     product(std::integral_constant<int, 3>{}, C::oG, C::oF, C::KVP);
-    if (MODE != 3) product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
+    if (MODE < 3) product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
 
     // accumulator element (s, g) of this lane: dyad (ld.i(g), ld.j(s))
     if (MODE == 2) {   // pairs, e0^2 + V0(i,j), e1^2 + V0(j,i), e0 e1 + C01 (no noise), fp64
@@ -318,6 +341,100 @@ ame_predict_pairs_kernel(PredictParams p) {
             double* o = p.partial + ((size_t)tl * ntile + tile) * AME_PROBIT_SUMS;
 #pragma unroll
             for (int q = 0; q < AME_PROBIT_SUMS; ++q) o[q] = sm[q];
+        }
+        return;
+    }
+    if (MODE == 4) {   // class histograms of t = E[mu] / sqrt(1 + V0), both entries of every selected pair
+        __shared__ unsigned hl[2 * AME_RANK_MAX_BINS];
+        const int nb = p.nbins;
+        for (int e = threadIdx.x; e < 2 * nb; e += AME_NT) hl[e] = 0u;
+        __syncthreads();
+        const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = ld.j(s);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = ld.i(g);
+                if (ame_upper_pair(i, j, n) && predict_pair_selected(p, tl, i, j)) {
+                    const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const bool tie = (c ? y.y : y.x) > 0.5f;
+                        const double t = (double)acc[c][s][g] / sqrt(1.0 + (double)acc[2 + c][s][g]);
+                        atomicAdd(&hl[(tie ? nb : 0) + predict_rank_bin(p, t)], 1u);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        unsigned long long* hs = p.hist + (size_t)tl * 2 * nb;
+        for (int e = threadIdx.x; e < 2 * nb; e += AME_NT) {
+            const unsigned v = hl[e];
+            if (v) atomicAdd(&hs[e], (unsigned long long)v);
+        }
+        return;
+    }
+    if (MODE == 5) {   // records of the entries at or above the slice's threshold bin
+        __shared__ unsigned lcnt;
+        __shared__ unsigned long long gbase;
+        if (threadIdx.x == 0) lcnt = 0u;
+        __syncthreads();
+        const int bmin = p.bin_min[tl], tf = p.tie_filter;
+        const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
+        unsigned take = 0u, ties = 0u;   // bit 8 s + 2 g + c of this lane's 32 entries
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = ld.j(s);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = ld.i(g);
+                if (ame_upper_pair(i, j, n) && predict_pair_selected(p, tl, i, j)) {
+                    const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const bool tie = (c ? y.y : y.x) > 0.5f;
+                        const double t = (double)acc[c][s][g] / sqrt(1.0 + (double)acc[2 + c][s][g]);
+                        const unsigned bit = 1u << (8 * s + 2 * g + c);
+                        if (tie) ties |= bit;
+                        if (predict_rank_bin(p, t) >= bmin && (tf < 0 || (int)tie == tf)) take |= bit;
+                    }
+                }
+            }
+        }
+        const unsigned mine = __popc(take);
+        const unsigned lbase = mine ? atomicAdd(&lcnt, mine) : 0u;
+        __syncthreads();
+        if (threadIdx.x == 0 && lcnt) gbase = atomicAdd(&p.count[tl], (unsigned long long)lcnt);
+        __syncthreads();
+        if (!mine) return;
+        const long long off = p.offset[tl];
+        const long long cap = p.offset[tl + 1] - off;   // <= 0: nothing is written
+        long long pos = (long long)(gbase + lbase);
+        ame_link_record* rs = p.rec + off;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = ld.j(s);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = ld.i(g);
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const unsigned bit = 1u << (8 * s + 2 * g + c);
+                    if (take & bit) {
+                        if (pos < cap) {   // beyond the region: counted, not written
+                            ame_link_record rc;
+                            rc.t = (double)acc[c][s][g] / sqrt(1.0 + (double)acc[2 + c][s][g]);
+                            rc.slice = p.slice0 + tl;
+                            rc.sender = c ? j : i;
+                            rc.receiver = c ? i : j;
+                            rc.tie = (ties & bit) ? 1 : 0;
+                            rs[pos] = rc;
+                        }
+                        ++pos;
+                    }
+                }
+            }
         }
         return;
     }
@@ -424,6 +541,8 @@ long long ame_mstep_dyad_work_doubles(const ame_dims* dm) {
 long long ame_probit_score_work_doubles(const ame_dims* dm) {
     return predict_feat_doubles(dm) + (long long)dm->T_local * ame_tri_tiles(dm->n) * AME_PROBIT_SUMS;
 }
+// ame_probit_rank / ame_probit_select keep nothing per tile: the feature rows only
+long long ame_probit_rank_work_doubles(const ame_dims* dm) { return predict_feat_doubles(dm); }
 long long ame_mstep_dyad_blocks(const ame_dims* dm) {
     const long long a = (long long)dm->T_local * dm->n, b = (long long)dm->T_local * ame_tri_tiles(dm->n);
     return a > b ? a : b;
@@ -457,6 +576,15 @@ static PredictParams predict_common(const ame_dims* dm, const float* x, const fl
     p.Mt = (const unsigned long long*)Mt;
     p.nw = ame_mask_row_words(n);
     p.mask_select = mask_select;
+    p.nbins = 1;
+    p.tie_filter = -1;
+    p.slice0 = 0;
+    p.t_max = p.scale = 1.0;
+    p.hist = nullptr;
+    p.bin_min = nullptr;
+    p.offset = nullptr;
+    p.count = nullptr;
+    p.rec = nullptr;
     return p;
 }
 
@@ -513,6 +641,61 @@ static int launch_probit_score(const ame_dims* dm, const ame_probit_score_args* 
     hipLaunchKernelGGL(ame_tile_sum_kernel<AME_PROBIT_SUMS>, dim3((unsigned)S), dim3(AME_NT), 0, st, p.partial,
                        p.ntile, a->sums);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// MODE 4: class histograms of the scores; hist is zeroed on the stream first
+template <int R>
+static int launch_probit_rank(const ame_dims* dm, const ame_probit_rank_args* a, hipStream_t st) {
+    const int S = dm->T_local;
+    PredictParams p = predict_common<R>(dm, a->x, a->cov, a->Yt, a->Mt, a->mask_select, a->work, st);
+    p.nbins = a->nbins;
+    p.t_max = a->t_max;
+    p.scale = a->scale;
+    p.hist = (unsigned long long*)a->hist;
+    if (hipMemsetAsync(a->hist, 0, (size_t)S * 2 * a->nbins * sizeof(uint64_t), st) != hipSuccess) return -3;
+    hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 4>), dim3((unsigned)((long long)S * p.ntile)),
+                       dim3(AME_NT), 0, st, p);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// MODE 5: records at or above bin_min; count is zeroed on the stream first
+template <int R>
+static int launch_probit_select(const ame_dims* dm, const ame_probit_select_args* a, hipStream_t st) {
+    const int S = dm->T_local;
+    PredictParams p = predict_common<R>(dm, a->x, a->cov, a->Yt, a->Mt, a->mask_select, a->work, st);
+    p.nbins = a->nbins;
+    p.t_max = a->t_max;
+    p.scale = a->scale;
+    p.bin_min = a->bin_min;
+    p.tie_filter = a->tie_filter;
+    p.slice0 = a->slice0;
+    p.offset = (const long long*)a->offset;
+    p.count = (unsigned long long*)a->count;
+    p.rec = a->records;
+    if (hipMemsetAsync(a->count, 0, (size_t)S * sizeof(uint64_t), st) != hipSuccess) return -3;
+    hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 5>), dim3((unsigned)((long long)S * p.ntile)),
+                       dim3(AME_NT), 0, st, p);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int AME_PFN(ame_probit_rank_dispatch)(const ame_dims* dm, const ame_probit_rank_args* a, hipStream_t st) {
+    switch (dm->r) {
+#define X(RR) \
+    case RR: return launch_probit_rank<RR>(dm, a, st);
+        AME_FOR_EACH_R(X)
+#undef X
+        default: return -1;
+    }
+}
+
+int AME_PFN(ame_probit_select_dispatch)(const ame_dims* dm, const ame_probit_select_args* a, hipStream_t st) {
+    switch (dm->r) {
+#define X(RR) \
+    case RR: return launch_probit_select<RR>(dm, a, st);
+        AME_FOR_EACH_R(X)
+#undef X
+        default: return -1;
+    }
 }
 
 int AME_PFN(ame_probit_score_dispatch)(const ame_dims* dm, const ame_probit_score_args* a, hipStream_t st) {

@@ -593,6 +593,71 @@ class DeviceEngine:
                 _lib.check(self.L.ame_probit_score(ctypes.byref(dm), ctypes.byref(a), sp), "ame_probit_score")
         return sums
 
+    def probit_rank(self, x, cov, Yt, nbins, t_max, Mt=None, mask_select=0):
+        """ame_probit_rank over a stack of slices: the class histograms
+        [S][2][nbins] (int64, device) of the scores t = E[mu] / sqrt(1 + V0) of
+        the 0 / 1 network Yt.  Whole slices at a time within the scratch budget
+        of predict(); integer counts, so a slice's row does not depend on the
+        split.  Runs on the ELBO stream; the caller has dropped speculation."""
+        from . import links
+        S = int(x.shape[0])
+        n, d = self.n, self.d
+        assert tuple(x.shape) == (S, n, d) and tuple(cov.shape) == (S, n, d, d)
+        assert x.is_contiguous() and cov.is_contiguous()
+        nbins, t_max = links.check_bins(nbins, t_max)
+        chunk, wk = self._slice_chunk(self.L.ame_probit_rank_work_size, S)
+        with torch.cuda.device(self.dev):
+            hist = torch.empty(S, 2, nbins, dtype=torch.int64, device=self.dev)
+        with self._elbo_call("probit_rank") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_probit_rank_args(
+                    x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]), Yt=_ptr(Yt[s0:s1]), hist=_ptr(hist[s0:s1]),
+                    work=_ptr(wk), work_doubles=wk.numel(),
+                    Mt=_ptr(Mt[s0:s1]) if Mt is not None else None, mask_select=int(mask_select),
+                    nbins=nbins, t_max=t_max, scale=links.scale(nbins, t_max))
+                _lib.check(self.L.ame_probit_rank(ctypes.byref(dm), ctypes.byref(a), sp), "ame_probit_rank")
+        return hist
+
+    def probit_select(self, x, cov, Yt, nbins, t_max, bin_min, offset, tie_filter=-1, Mt=None, mask_select=0):
+        """ame_probit_select over a stack of slices: every selected entry whose
+        bin is at least bin_min[s] (and whose class is tie_filter, if 0 or 1)
+        as a record in slice s's region [offset[s], offset[s + 1]).  bin_min
+        (S,) and offset (S + 1,) are host integers.  Returns (records: int64
+        words on the device, 3 per record, links.RECORD; count (S,) int64:
+        the entries that passed, which exceeds a region's size where some were
+        dropped).  Chunked like probit_rank; runs on the ELBO stream."""
+        from . import links
+        S = int(x.shape[0])
+        n, d = self.n, self.d
+        assert tuple(x.shape) == (S, n, d) and tuple(cov.shape) == (S, n, d, d)
+        assert x.is_contiguous() and cov.is_contiguous()
+        nbins, t_max = links.check_bins(nbins, t_max)
+        off = torch.as_tensor(offset, dtype=torch.int64).reshape(-1)
+        bmin = torch.as_tensor(bin_min, dtype=torch.int32).reshape(-1)
+        if off.numel() != S + 1 or bmin.numel() != S or int(off[0]) < 0 or bool((off[1:] < off[:-1]).any()):
+            raise ValueError("probit_select: offset must hold S + 1 non-decreasing record offsets from >= 0 "
+                             "and bin_min S bins")
+        chunk, wk = self._slice_chunk(self.L.ame_probit_select_work_size, S)
+        with torch.cuda.device(self.dev):
+            rec = torch.zeros(max(1, int(off[-1])) * (links.RECORD.itemsize // 8), dtype=torch.int64,
+                              device=self.dev)
+            count = torch.empty(S, dtype=torch.int64, device=self.dev)
+            d_off, d_bmin = off.to(self.dev), bmin.to(self.dev)
+        with self._elbo_call("probit_select") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_probit_select_args(
+                    x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]), Yt=_ptr(Yt[s0:s1]), work=_ptr(wk),
+                    work_doubles=wk.numel(), Mt=_ptr(Mt[s0:s1]) if Mt is not None else None,
+                    mask_select=int(mask_select), nbins=nbins, t_max=t_max, scale=links.scale(nbins, t_max),
+                    bin_min=_ptr(d_bmin[s0:s1]), tie_filter=int(tie_filter), slice0=s0,
+                    offset=_ptr(d_off[s0:s1 + 1]), count=_ptr(count[s0:s1]), records=_ptr(rec))
+                _lib.check(self.L.ame_probit_select(ctypes.byref(dm), ctypes.byref(a), sp), "ame_probit_select")
+        return rec, count
+
     def mask_args(self, select):
         """(Yt, Mt, mask_select) for predict / mstep_stats: the packed observations
         (never the working network) with the mask and a selector, or the

@@ -342,6 +342,111 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
         pi = 0.5 * torch.erfc(-(dd[..., 0:2] / torch.sqrt(1.0 + dd[..., 2:4])) * math.sqrt(0.5))
         return pi.float().permute(1, 2, 0, 3).to("cpu").contiguous()
 
+    # ---------------- ranking the links of a binary network (extension) ----------------
+    # ROC / precision-recall curves, AUC and ranked lists from the scores
+    # t = E[mu] / sqrt(1 + V0) (pi = Phi(t) is monotone in t), formed tile by
+    # tile on the device (ame_probit_rank / ame_probit_select); no probability
+    # is moved to the host.  The host finish is ame_amd/links.py.
+    def _links_engine(self, what):
+        if not self._binary():
+            raise ValueError(f"{what} needs a binary model (model.set_binary)")
+        if self._time_sharded():
+            raise NotImplementedError(f"{what} is not available on a time-sharded run: fit on one process")
+        return self._predict_engine()
+
+    @staticmethod
+    def _top_links(eng, x, cov, Yt, Mt, select, hist, k, ties, bins, t_max, max_records):
+        """top_links' fields for a stack of slices whose histograms are `hist`."""
+        import numpy as np
+        from .. import links
+        bin_min, capacity = links.threshold(hist, k, ties)
+        total = int(capacity.sum())
+        if total > int(max_records):
+            raise ValueError(f"{total} candidate records exceed max_records={int(max_records)}: too many scores "
+                             f"share the threshold bin (they saturate the clamped end bin beyond t_max={t_max}, or "
+                             f"bins={bins} is too coarse); raise t_max or bins, or ask for fewer slices")
+        offset = np.concatenate([[0], np.cumsum(capacity)]).astype(np.int64)
+        rec, count = eng.probit_select(x, cov, Yt, bins, t_max, bin_min, offset,
+                                       tie_filter=-1 if ties is None else int(ties), Mt=Mt, mask_select=select)
+        count = count.to("cpu").numpy()
+        if not np.array_equal(count, capacity):   # the two passes bin the same scores: cannot differ
+            raise RuntimeError(f"ame_probit_select passed {count.tolist()} entries, the histograms "
+                               f"promise {capacity.tolist()}")
+        records = rec.to("cpu").numpy().view(links.RECORD)[:total]
+        out = links.top_k(records, offset, k)
+        out["prob"] = links.phi(out["score"])
+        return out
+
+    def link_roc(self, subset=None, bins=1024, t_max=8.0) -> dict:
+        """ROC and precision-recall curves and the AUC of the ties of a binary
+        model, per time step, from device histograms of the score t = E[mu] /
+        sqrt(1 + V0) (pi = Phi(t) is monotone in it; class 1 is a tie).  ``subset``
+        as in :meth:`predictive_check` ("held_out": the hidden pairs against
+        ``model.Y``, out of sample).  ``bins`` (1 .. 2048) equal bins cover
+        [-t_max, t_max); the end bins also hold what lies beyond.  Returns
+        ``edges`` (bins + 1,), ``hist`` (T, 2, bins) int64, ``pairs`` /
+        ``positives`` / ``negatives`` (T,), ``auc``, ``auc_lo``, ``auc_hi``,
+        ``average_precision`` (T,), ``fpr`` / ``tpr`` / ``precision`` / ``recall``
+        (T, bins + 1) and the same over all steps under ``pooled``
+        (:func:`ame_amd.links.curves`).  The exact AUC of the scores lies in
+        [auc_lo, auc_hi]; a step with one class only gives NaN."""
+        from .. import links
+        eng = self._links_engine("link_roc")
+        bins, t_max = links.check_bins(bins, t_max)
+        select = self._subset(subset)
+        Yt, Mt, select = eng.mask_args(select)
+        hist = eng.probit_rank(eng.x_a, eng.cov, Yt, bins, t_max, Mt=Mt, mask_select=select)
+        return links.roc(hist.to("cpu").numpy(), bins, t_max)
+
+    def top_links(self, k=100, subset=None, ties=None, bins=1024, t_max=8.0, max_records=2 ** 24) -> dict:
+        """The k most probable directed links of every time step of a binary
+        model, best first by (-score, sender, receiver): ``sender``, ``receiver``,
+        ``tie`` (T, k) int64, ``score`` (T, k) fp64 = t and ``prob`` = Phi(score);
+        a step with fewer than k candidates is padded with -1 / NaN.  ``ties=0``
+        ranks the absent links only (recommendation on an observed network),
+        ``ties=1`` the present ones.  The device keeps the entries at or above
+        the histogram bin that holds the k-th score; more than ``max_records``
+        of them is a ValueError (many scores saturate the clamped top bin: raise
+        ``t_max`` or ``bins``)."""
+        from .. import links
+        eng = self._links_engine("top_links")
+        bins, t_max = links.check_bins(bins, t_max)
+        if isinstance(k, bool) or int(k) != k or int(k) < 1:
+            raise ValueError(f"k must be an integer >= 1 (got {k!r})")
+        if ties not in (None, 0, 1):
+            raise ValueError(f"ties must be None, 0 or 1 (got {ties!r})")
+        select = self._subset(subset)
+        Yt, Mt, select = eng.mask_args(select)
+        hist = eng.probit_rank(eng.x_a, eng.cov, Yt, bins, t_max, Mt=Mt, mask_select=select)
+        return self._top_links(eng, eng.x_a, eng.cov, Yt, Mt, select, hist.to("cpu").numpy(), int(k), ties,
+                               bins, t_max, max_records)
+
+    def forecast_links(self, B_future, bins=1024, t_max=8.0, k=0, max_records=2 ** 24) -> dict:
+        """:meth:`link_roc` of held-out steps: ``B_future`` (n, n, h) bool / uint8
+        ties scored against the h-step forecast of the states (:meth:`forecast`);
+        the same dictionary with h rows, every future pair observed, plus
+        :meth:`top_links`' fields (both classes) when k > 0."""
+        from .. import links
+        eng = self._links_engine("forecast_links")
+        bins, t_max = links.check_bins(bins, t_max)
+        if isinstance(k, bool) or int(k) != k or int(k) < 0:
+            raise ValueError(f"k must be an integer >= 0 (got {k!r})")
+        B = torch.as_tensor(B_future)
+        if B.dim() != 3 or tuple(B.shape[:2]) != (self.n, self.n) or B.shape[2] < 1:
+            raise ValueError(f"B_future has shape {tuple(B.shape)}, expected ({self.n}, {self.n}, h)")
+        if B.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"B_future has dtype {B.dtype}, expected bool or uint8")
+        # the 0 / 1 network as set_binary builds model.Y: no self ties, entry (ij, ji)
+        Bc = (B.to("cpu") != 0) & ~torch.eye(self.n, dtype=torch.bool).unsqueeze(2)
+        Y01 = torch.stack([Bc, Bc.transpose(0, 1)], dim=-1).float()
+        eng, (m, S) = self._forecast_states(int(B.shape[2]))
+        Yt = eng.pack_future(Y01)
+        hist = eng.probit_rank(m, S, Yt, bins, t_max).to("cpu").numpy()
+        out = links.roc(hist, bins, t_max)
+        if int(k) > 0:
+            out.update(self._top_links(eng, m, S, Yt, None, 0, hist, int(k), None, bins, t_max, max_records))
+        return out
+
     # ---------------- exact smoothing across time (extension) ----------------
     def smooth(self, partners=None) -> SmoothResult:
         """Each node's exact Gaussian posterior over its whole trajectory given
