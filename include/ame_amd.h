@@ -52,6 +52,10 @@
  *   ame_probit_rank,  replace nothing in the reference: ranking the links of a binary
  *   ame_probit_select network (per-slice class histograms of the scores for ROC / AUC;
  *                     the records of the highest-scoring entries for a top-k list).
+ *   ame_resid_nodes,  replace nothing in the reference: residual diagnostics of a
+ *   ame_resid_hist,   Gaussian fit (per-node sums of the dyad scores; the per-slice
+ *   ame_resid_select  histogram of the Mahalanobis distance m^2; the records of the
+ *                     most surprising pairs for a top-k list).
  *
  * Conventions: all pointers are DEVICE pointers (hipMalloc / torch CUDA
  * tensors) unless the field says otherwise; `stream` is a hipStream_t (NULL =
@@ -819,6 +823,107 @@ int ame_probit_select(const ame_dims* dims, const ame_probit_select_args* args, 
 /* Scratch doubles: the feature rows of ame_predict; -1 on bad dims. */
 long long ame_probit_rank_work_size(const ame_dims* dims);
 long long ame_probit_select_work_size(const ame_dims* dims);
+
+/* ---- residual diagnostics: per-node sums, the distribution of m^2, the top residuals ----
+ * Replaces nothing the reference computes.  The Gaussian counterpart of the link
+ * ranking above: three more epilogues of ame_predict's tile kernel, on its feature
+ * rows and all five products.  Pairs i < j are selected by Mt / mask_select exactly
+ * as in ame_predict's scoring, and the per-pair quantities are the ones it forms, in
+ * fp64, with `noise` as in ame_predict_args:
+ *   e = Yt[s][i][j] - E[mu_pair],  Sigma = [[V0(i,j) + n00, C01 + n01], [., V0(j,i) + n11]],
+ *   m^2 = e' Sigma^-1 e,  z^2_c = e_c^2 / Sigma_cc,  log N(y; E[mu], Sigma).
+ * Entry 0 of pair (i, j) is i -> j: i sends it and j receives it; entry 1 is the reverse.
+ *
+ * ame_resid_nodes: node[s][i][AME_NODE_SUMS], fp64, sums over the selected pairs that
+ * contain node i (a node with none gets exact zeros):
+ *   [0] pairs   [1] sum log N of the pair   [2] sum m^2
+ *   [3], [4] sum z^2 of the entries i sends / receives
+ *   [5], [6] sum e   of the entries i sends / receives (signed: the bias)
+ *   [7], [8] sum e^2 of the entries i sends / receives
+ * No atomics.  In tile (I, J) a row node's 64 pairs are added in the lane and across
+ * its 16-lane row, a column node's in the lane, across the four lane quarters and, in
+ * wave order, across the four waves, all in a fixed order.  With nb = ceil(n / 64) a
+ * node of block B gets exactly nb + 1 contributions: as a column node of tiles
+ * (I' <= B, B), slot I', and as a row node of tiles (B, J >= B), slot J + 1.  Each is
+ * stored once into a [S][nb + 1][n][AME_NODE_SUMS] partial in `work` (zeros where
+ * nothing is selected; nothing is cleared) and a second kernel adds a node's slots in
+ * slot order: the same bits from run to run, for any split of the slices over calls
+ * and for both slice mappings.
+ *
+ * ame_resid_hist: hist[s][b] = selected pairs of slice s whose m^2 falls into bin b,
+ * uint64.  The bin is, in fp64,
+ *   b = floor(m2 * scale)   clamped to [0, nbins - 1],   scale = nbins / m2_max
+ * computed once by the caller: one multiply, nothing a compiler can contract.  A NaN
+ * m^2 goes to bin nbins - 1, NOT to bin 0 as a NaN score of ame_probit_rank does, on
+ * purpose: a broken pair must surface among the most surprising ones instead of
+ * hiding among the best fitted.  The mechanism is ame_probit_rank's (the call zeroes
+ * hist on its stream; a uint32 histogram per workgroup in LDS, LDS integer atomics,
+ * non-zero bins added with global 64-bit integer atomics).
+ *
+ * ame_resid_select: the same pass; every selected pair with b >= bin_min[s] becomes a
+ * record in records[offset[s] .. offset[s + 1]), by ame_probit_select's reservation
+ * scheme (count[s] zeroed by the call; one global integer atomic per workgroup; plain
+ * stores; a pair beyond the region is counted and not written; the order inside a
+ * region is free).  z_c = e_c / sqrt(Sigma_cc), signed.  No floating-point atomics
+ * anywhere. */
+#define AME_NODE_SUMS 9
+typedef struct ame_resid_nodes_args {
+    const float* x;        /* [S][n][d] means              (S = dims.T_local)           */
+    const float* cov;      /* [S][n][d][d] covariances                                  */
+    const float* Yt;       /* [S][n][ny][2] packed network (ame_pack_y)                 */
+    double noise[4];       /* N row-major, as ame_predict_args                          */
+    double* node;          /* [S][n][AME_NODE_SUMS] fp64, overwritten                   */
+    double* work;          /* >= ame_resid_nodes_work_size() doubles                    */
+    uint64_t work_doubles; /* size of `work` in doubles, checked                        */
+    const uint64_t* Mt;    /* [S][n][nw] packed mask (ame_pack_mask), or NULL           */
+    int32_t mask_select;   /* 0, AME_MASK_OBSERVED or AME_MASK_HIDDEN (needs Mt)        */
+} ame_resid_nodes_args;
+typedef struct ame_resid_hist_args {
+    const float* x;        /* as ame_resid_nodes_args                                   */
+    const float* cov;
+    const float* Yt;
+    double noise[4];
+    uint64_t* hist;        /* [S][nbins] uint64, overwritten                            */
+    double* work;          /* >= ame_resid_hist_work_size() doubles                     */
+    uint64_t work_doubles;
+    const uint64_t* Mt;
+    int32_t mask_select;
+    int32_t nbins;         /* 1 .. AME_RANK_MAX_BINS                                    */
+    double scale;          /* nbins / m2_max in fp64, > 0                               */
+} ame_resid_hist_args;
+typedef struct ame_resid_record {
+    double m2;             /* e' Sigma^-1 e                                             */
+    double z0, z1;         /* e_c / sqrt(Sigma_cc), signed                              */
+    int32_t slice;         /* slice0 + the slice's index in the call                    */
+    int32_t i, j;          /* the pair, i < j                                           */
+    int32_t pad;           /* 0                                                         */
+} ame_resid_record;
+typedef struct ame_resid_select_args {
+    const float* x;        /* as ame_resid_hist_args                                    */
+    const float* cov;
+    const float* Yt;
+    double noise[4];
+    double* work;          /* >= ame_resid_select_work_size() doubles                   */
+    uint64_t work_doubles;
+    const uint64_t* Mt;
+    int32_t mask_select;
+    int32_t nbins;
+    double scale;
+    const int32_t* bin_min; /* [S] smallest bin taken                                   */
+    int32_t slice0;        /* added to the slice index of a record                      */
+    int32_t reserved;      /* 0                                                         */
+    const int64_t* offset; /* [S + 1] non-decreasing record offsets of the regions      */
+    uint64_t* count;       /* [S] pairs that passed, overwritten                        */
+    ame_resid_record* records; /* offset[S] records                                     */
+} ame_resid_select_args;
+int ame_resid_nodes(const ame_dims* dims, const ame_resid_nodes_args* args, void* stream);
+int ame_resid_hist(const ame_dims* dims, const ame_resid_hist_args* args, void* stream);
+int ame_resid_select(const ame_dims* dims, const ame_resid_select_args* args, void* stream);
+/* Scratch doubles: the feature rows of ame_predict, for ame_resid_nodes plus
+ * T_local (nb + 1) n AME_NODE_SUMS; -1 on bad dims. */
+long long ame_resid_nodes_work_size(const ame_dims* dims);
+long long ame_resid_hist_work_size(const ame_dims* dims);
+long long ame_resid_select_work_size(const ame_dims* dims);
 
 /* A HIP stream whose kernels run only on compute units [first_cu, first_cu +
  * num_cus) of the current device (hipExtStreamCreateWithCUMask); *stream

@@ -160,9 +160,35 @@ class ame_probit_select_args(ctypes.Structure):
                 ("offset", c_vp), ("count", c_vp), ("records", c_vp)]
 
 
+AME_NODE_SUMS = 9
+
+
+class ame_resid_nodes_args(ctypes.Structure):
+    _fields_ = [("x", c_vp), ("cov", c_vp), ("Yt", c_vp), ("noise", ctypes.c_double * 4), ("node", c_vp),
+                ("work", c_vp), ("work_doubles", ctypes.c_uint64), ("Mt", c_vp), ("mask_select", c_int32)]
+
+
+class ame_resid_hist_args(ctypes.Structure):
+    _fields_ = [("x", c_vp), ("cov", c_vp), ("Yt", c_vp), ("noise", ctypes.c_double * 4), ("hist", c_vp),
+                ("work", c_vp), ("work_doubles", ctypes.c_uint64), ("Mt", c_vp), ("mask_select", c_int32),
+                ("nbins", c_int32), ("scale", ctypes.c_double)]
+
+
+class ame_resid_record(ctypes.Structure):
+    _fields_ = [("m2", ctypes.c_double), ("z0", ctypes.c_double), ("z1", ctypes.c_double), ("slice", c_int32),
+                ("i", c_int32), ("j", c_int32), ("pad", c_int32)]
+
+
+class ame_resid_select_args(ctypes.Structure):
+    _fields_ = [("x", c_vp), ("cov", c_vp), ("Yt", c_vp), ("noise", ctypes.c_double * 4), ("work", c_vp),
+                ("work_doubles", ctypes.c_uint64), ("Mt", c_vp), ("mask_select", c_int32), ("nbins", c_int32),
+                ("scale", ctypes.c_double), ("bin_min", c_vp), ("slice0", c_int32), ("reserved", c_int32),
+                ("offset", c_vp), ("count", c_vp), ("records", c_vp)]
+
+
 # every symbol include/ame_amd.h declares (checked by tests/test_capi.py)
 EXPORTS = ("ame_pack_y", "ame_pack_y_size", "ame_sweep", "ame_sweep_kind", "ame_sweep_work_size", "ame_sweep_orders_slices", "ame_sweep_max_slices", "ame_sweep_slice_workgroups", "ame_sweep_lds_bytes", "ame_cov",
-           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_smooth", "ame_smooth_work_size", "ame_smooth_masked_work_size", "ame_smooth_lds_bytes", "ame_covar_stats", "ame_covar_work_size", "ame_covar_resid", "ame_mask_words", "ame_pack_mask", "ame_fill_missing", "ame_fill_work_size", "ame_net_moments", "ame_net_triads", "ame_simulate", "ame_net_moments_work_size", "ame_net_triads_work_size", "ame_probit_fill", "ame_probit_score", "ame_probit_fill_work_size", "ame_probit_score_work_size", "ame_probit_rank", "ame_probit_select", "ame_probit_rank_work_size", "ame_probit_select_work_size", "ame_host_register", "ame_host_unregister",
+           "ame_elbo", "ame_elbo_work_size", "ame_elbo_pairs_diag", "ame_predict", "ame_predict_work_size", "ame_mstep_stats", "ame_mstep_work_size", "ame_smooth", "ame_smooth_work_size", "ame_smooth_masked_work_size", "ame_smooth_lds_bytes", "ame_covar_stats", "ame_covar_work_size", "ame_covar_resid", "ame_mask_words", "ame_pack_mask", "ame_fill_missing", "ame_fill_work_size", "ame_net_moments", "ame_net_triads", "ame_simulate", "ame_net_moments_work_size", "ame_net_triads_work_size", "ame_probit_fill", "ame_probit_score", "ame_probit_fill_work_size", "ame_probit_score_work_size", "ame_probit_rank", "ame_probit_select", "ame_probit_rank_work_size", "ame_probit_select_work_size", "ame_resid_nodes", "ame_resid_hist", "ame_resid_select", "ame_resid_nodes_work_size", "ame_resid_hist_work_size", "ame_resid_select_work_size", "ame_host_register", "ame_host_unregister",
            "ame_stream_create_cu_range", "ame_stream_destroy",
            "ame_peer_alloc", "ame_peer_free", "ame_peer_open", "ame_peer_close",
            "ame_peer_probe", "ame_peer_read_u64", "ame_peer_clear",
@@ -246,6 +272,12 @@ def _declare(L):
     L.ame_probit_rank_work_size.restype = ctypes.c_longlong
     L.ame_probit_select_work_size.argtypes = [P(ame_dims)]
     L.ame_probit_select_work_size.restype = ctypes.c_longlong
+    for name, args in (("ame_resid_nodes", ame_resid_nodes_args), ("ame_resid_hist", ame_resid_hist_args),
+                       ("ame_resid_select", ame_resid_select_args)):
+        getattr(L, name).argtypes = [P(ame_dims), P(args), c_vp]
+        getattr(L, name).restype = ctypes.c_int
+        getattr(L, name + "_work_size").argtypes = [P(ame_dims)]
+        getattr(L, name + "_work_size").restype = ctypes.c_longlong
     L.ame_debug_selftest.argtypes = [c_vp, c_vp]
     L.ame_debug_selftest.restype = ctypes.c_int
     if hasattr(L, "ame_debug_occupy"):   # diagnostic; absent from older A/B builds

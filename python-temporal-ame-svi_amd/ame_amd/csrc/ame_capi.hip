@@ -715,6 +715,95 @@ int ame_probit_select(const ame_dims* dims, const ame_probit_select_args* a, voi
     return launched(ame_probit_select_dispatch(dims, a, (hipStream_t)stream), "probit_select");
 }
 
+long long ame_resid_nodes_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_resid_nodes_work_doubles(dims);
+}
+
+long long ame_resid_hist_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_probit_rank_work_doubles(dims);
+}
+
+long long ame_resid_select_work_size(const ame_dims* dims) {
+    if (check_dims(dims)) return -1;
+    return ame_probit_rank_work_doubles(dims);
+}
+
+// what the three residual entry points share: the noise, the scratch and the launch size
+static int check_resid_common(const char* who, const ame_dims* dims, const double* noise, long long need,
+                              unsigned long long work_doubles) {
+    const long long b1 = (long long)dims->T_local * dims->n, b2 = (long long)dims->T_local * ame_tri_tiles(dims->n);
+    if (!(noise[0] == noise[0] && noise[1] == noise[1] && noise[2] == noise[2] && noise[3] == noise[3]))
+        snprintf(g_err, sizeof(g_err), "%s: noise holds a NaN", who);
+    else if ((long long)work_doubles < need)
+        snprintf(g_err, sizeof(g_err), "%s: work holds fewer doubles than %s_work_size", who, who);
+    else if ((b1 > b2 ? b1 : b2) > 0x7FFFFFFFLL)
+        snprintf(g_err, sizeof(g_err), "%s: T_local=%d slices of n=%d exceed one launch; pass fewer slices", who,
+                 dims->T_local, dims->n);
+    else
+        return 0;
+    return -1;
+}
+
+// the bin rule of ame_resid_hist / ame_resid_select
+static int check_resid_bins(const char* who, int nbins, double scale) {
+    if (nbins < 1 || nbins > AME_RANK_MAX_BINS)
+        snprintf(g_err, sizeof(g_err), "%s: nbins=%d outside [1, %d]", who, nbins, AME_RANK_MAX_BINS);
+    else if (!(scale > 0.0) || !(scale < 1e300))
+        snprintf(g_err, sizeof(g_err), "%s: scale must be positive and finite", who);
+    else
+        return 0;
+    return -1;
+}
+
+int ame_resid_nodes(const ame_dims* dims, const ame_resid_nodes_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_resid_nodes: args is NULL");
+    if (!a->x || !a->cov || !a->Yt || !a->node || !a->work)
+        return fail("ame_resid_nodes: NULL buffer (x, cov, Yt, node, work)");
+    if (int e = check_mask_select("ame_resid_nodes", a->mask_select, a->Mt)) return e;
+    if (((uintptr_t)a->Yt | (uintptr_t)a->Mt | (uintptr_t)a->node | (uintptr_t)a->work) & 7)
+        return fail("ame_resid_nodes: Yt, Mt, node and work must be 8-byte aligned");
+    if (int e = check_resid_common("ame_resid_nodes", dims, a->noise, ame_resid_nodes_work_doubles(dims),
+                                   a->work_doubles))
+        return e;
+    return launched(ame_resid_nodes_dispatch(dims, a, (hipStream_t)stream), "resid_nodes");
+}
+
+int ame_resid_hist(const ame_dims* dims, const ame_resid_hist_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_resid_hist: args is NULL");
+    if (!a->x || !a->cov || !a->Yt || !a->hist || !a->work)
+        return fail("ame_resid_hist: NULL buffer (x, cov, Yt, hist, work)");
+    if (int e = check_mask_select("ame_resid_hist", a->mask_select, a->Mt)) return e;
+    if (((uintptr_t)a->Yt | (uintptr_t)a->Mt | (uintptr_t)a->hist | (uintptr_t)a->work) & 7)
+        return fail("ame_resid_hist: Yt, Mt, hist and work must be 8-byte aligned");
+    if (int e = check_resid_bins("ame_resid_hist", a->nbins, a->scale)) return e;
+    if (int e = check_resid_common("ame_resid_hist", dims, a->noise, ame_probit_rank_work_doubles(dims),
+                                   a->work_doubles))
+        return e;
+    return launched(ame_resid_hist_dispatch(dims, a, (hipStream_t)stream), "resid_hist");
+}
+
+int ame_resid_select(const ame_dims* dims, const ame_resid_select_args* a, void* stream) {
+    if (int e = check_dims(dims)) return e;
+    if (!a) return fail("ame_resid_select: args is NULL");
+    if (!a->x || !a->cov || !a->Yt || !a->work || !a->bin_min || !a->offset || !a->count || !a->records)
+        return fail("ame_resid_select: NULL buffer (x, cov, Yt, work, bin_min, offset, count, records)");
+    if (int e = check_mask_select("ame_resid_select", a->mask_select, a->Mt)) return e;
+    if (((uintptr_t)a->Yt | (uintptr_t)a->Mt | (uintptr_t)a->work | (uintptr_t)a->offset | (uintptr_t)a->count |
+         (uintptr_t)a->records) & 7)
+        return fail("ame_resid_select: Yt, Mt, work, offset, count and records must be 8-byte aligned");
+    if ((uintptr_t)a->bin_min & 3) return fail("ame_resid_select: bin_min must be 4-byte aligned");
+    if (a->slice0 < 0) return fail("ame_resid_select: slice0=%d is negative", a->slice0);
+    if (int e = check_resid_bins("ame_resid_select", a->nbins, a->scale)) return e;
+    if (int e = check_resid_common("ame_resid_select", dims, a->noise, ame_probit_rank_work_doubles(dims),
+                                   a->work_doubles))
+        return e;
+    return launched(ame_resid_select_dispatch(dims, a, (hipStream_t)stream), "resid_select");
+}
+
 long long ame_smooth_work_size(const ame_dims* dims, int nodes) {
     if (check_dims(dims)) return -1;
     if (nodes < 1 || nodes > dims->n) return fail("ame_smooth_work_size: nodes=%d outside [1, n]", nodes);

@@ -87,5 +87,10 @@ long long ame_probit_score_work_doubles(const ame_dims*);
 AME_SPLIT_FN(int, ame_probit_rank_dispatch, (const ame_dims*, const ame_probit_rank_args*, hipStream_t))
 AME_SPLIT_FN(int, ame_probit_select_dispatch, (const ame_dims*, const ame_probit_select_args*, hipStream_t))
 long long ame_probit_rank_work_doubles(const ame_dims*);
+// ame_predict.hip (MODE 6 - 8: per-node residual sums, the histogram of m^2, the top residuals)
+AME_SPLIT_FN(int, ame_resid_nodes_dispatch, (const ame_dims*, const ame_resid_nodes_args*, hipStream_t))
+AME_SPLIT_FN(int, ame_resid_hist_dispatch, (const ame_dims*, const ame_resid_hist_args*, hipStream_t))
+AME_SPLIT_FN(int, ame_resid_select_dispatch, (const ame_dims*, const ame_resid_select_args*, hipStream_t))
+long long ame_resid_nodes_work_doubles(const ame_dims*);
 
 #undef AME_SPLIT_FN

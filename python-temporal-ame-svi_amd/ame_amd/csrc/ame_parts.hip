@@ -68,6 +68,27 @@ int ame_probit_select_dispatch(const ame_dims* dm, const ame_probit_select_args*
         default: return ame_probit_select_dispatch_p2(dm, a, st);
     }
 }
+int ame_resid_nodes_dispatch(const ame_dims* dm, const ame_resid_nodes_args* a, hipStream_t st) {
+    switch (dm->r % 3) {
+        case 0: return ame_resid_nodes_dispatch_p0(dm, a, st);
+        case 1: return ame_resid_nodes_dispatch_p1(dm, a, st);
+        default: return ame_resid_nodes_dispatch_p2(dm, a, st);
+    }
+}
+int ame_resid_hist_dispatch(const ame_dims* dm, const ame_resid_hist_args* a, hipStream_t st) {
+    switch (dm->r % 3) {
+        case 0: return ame_resid_hist_dispatch_p0(dm, a, st);
+        case 1: return ame_resid_hist_dispatch_p1(dm, a, st);
+        default: return ame_resid_hist_dispatch_p2(dm, a, st);
+    }
+}
+int ame_resid_select_dispatch(const ame_dims* dm, const ame_resid_select_args* a, hipStream_t st) {
+    switch (dm->r % 3) {
+        case 0: return ame_resid_select_dispatch_p0(dm, a, st);
+        case 1: return ame_resid_select_dispatch_p1(dm, a, st);
+        default: return ame_resid_select_dispatch_p2(dm, a, st);
+    }
+}
 int ame_mstep_dyad_dispatch(const ame_dims* dm, const ame_mstep_args* a, double* work, hipStream_t st) {
     switch (dm->r % 3) {
         case 0: return ame_mstep_dyad_dispatch_p0(dm, a, work, st);

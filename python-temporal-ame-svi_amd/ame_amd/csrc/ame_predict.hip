@@ -40,8 +40,18 @@
 // MODE 5 of K2 (ame_probit_select): the same pass; entries at or above the
 //    slice's threshold bin are appended to the slice's region of records (one
 //    global integer atomic per workgroup reserves its run).
-// Modes 0 - 3: no atomics, no spin, no O(n^2) intermediate.  Modes 4, 5: integer
-// atomics only (order-independent sums / a free order the host sorts away).
+// MODE 6 of K2 (ame_resid_nodes): MODE 0's products and per-pair quantities; the
+//    epilogue adds them per node, a few slots at a time so that the sums fit
+//    beside the 20 accumulators: a row node's 64 pairs in the lane and across its
+//    16-lane row, a column node's in the lane, across the lane quarters and (LDS)
+//    across the waves, each result stored once into its own slot of a
+//    [S][nb + 1][n][AME_NODE_SUMS] partial that ame_col_sum adds in slot order.
+// MODE 7 of K2 (ame_resid_hist): the same pairs; m^2 binned as MODE 4 bins t
+//    (one uint32 [nbins] histogram in LDS), a NaN into the last bin.
+// MODE 8 of K2 (ame_resid_select): MODE 5's reservation scheme for the pairs at
+//    or above the slice's threshold bin of m^2.
+// Modes 0 - 3, 6: no atomics, no spin, no O(n^2) intermediate.  Modes 4, 5, 7, 8:
+// integer atomics only (order-independent sums / a free order the host sorts away).
 #include <type_traits>
 
 #include "ame_tile.h"
@@ -88,6 +98,9 @@ struct PredictParams {
     const long long* offset;        // [S + 1] record offsets of the slices' regions
     unsigned long long* count;      // [S] entries that passed (also those beyond a region)
     ame_link_record* rec;
+    // MODE 6: node partial [S][nb + 1][n][AME_NODE_SUMS]; MODE 8: the records
+    double* node_partial;
+    ame_resid_record* rrec;
 };
 
 // whether pair (i, j), i < j < n, of slice tl is selected (MODE 0 scoring, MODE 2 statistics)
@@ -104,6 +117,31 @@ __device__ __forceinline__ int predict_rank_bin(const PredictParams& p, double t
     const double fb = floor((t + p.t_max) * p.scale);
     return !(fb >= 0.0) ? 0 : (fb > (double)(p.nbins - 1) ? p.nbins - 1 : (int)fb);
 }
+
+// the histogram bin of a pair's m^2 (include/ame_amd.h): one multiply, then floor,
+// clamped to [0, nbins - 1]; a NaN m^2 goes to bin nbins - 1 (not 0 as above)
+__device__ __forceinline__ int resid_bin(const PredictParams& p, double m2) {
+    const double fb = floor(m2 * p.scale);
+    return !(fb <= (double)(p.nbins - 1)) ? p.nbins - 1 : (fb < 0.0 ? 0 : (int)fb);
+}
+
+// MODE 0's per-pair quantities (modes 6 - 8), from the pair's observation and its
+// five products
+struct ResidPair {
+    double e0, e1, v0, v1, c, det, q0, q1, m2;
+    __device__ __forceinline__ ResidPair(const PredictParams& p, float2 y, float a0, float a1, float a2, float a3,
+                                         float a4) {
+        e0 = (double)y.x - (double)a0;
+        e1 = (double)y.y - (double)a1;
+        v0 = (double)a2 + p.n00;
+        v1 = (double)a3 + p.n11;
+        c = (double)a4 + p.n01;
+        det = v0 * v1 - c * c;
+        q0 = e0 * e0;
+        q1 = e1 * e1;
+        m2 = (v1 * q0 - 2.0 * c * e0 * e1 + v0 * q1) / det;
+    }
+};
 
 // ---------------------------------------------------------------------------
 // K1: feature rows
@@ -275,7 +313,8 @@ ame_predict_pairs_kernel(PredictParams p) {
     product(std::integral_constant<int, 1>{}, C::oMb, C::oMa, C::MP);
     product(std::integral_constant<int, 2>{}, C::oF, C::oG, C::KVP);
     product(std::integral_constant<int, 3>{}, C::oG, C::oF, C::KVP);
-    if (MODE < 3) product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
+    constexpr bool NEED_C01 = MODE < 3 || MODE >= 6;   // the Bernoulli modes 3 - 5 skip C01
+    if (NEED_C01) product(std::integral_constant<int, 4>{}, C::oP, C::oQ, C::KCP);
 
     // accumulator element (s, g) of this lane: dyad (ld.i(g), ld.j(s))
     if (MODE == 2) {   // pairs, e0^2 + V0(i,j), e1^2 + V0(j,i), e0 e1 + C01 (no noise), fp64
@@ -438,6 +477,186 @@ ame_predict_pairs_kernel(PredictParams p) {
         }
         return;
     }
+    if (MODE == 6) {   // per-node sums of MODE 0's per-pair quantities, a few slots per pass
+        constexpr int KMAX = 4;
+        __shared__ double cl[4][AME_DT][KMAX];   // column partials of the four waves
+        constexpr double LOG2PI2 = 2.0 * 1.8378770664093454835606594728112;
+        const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
+        const int nb = (n + AME_DT - 1) / AME_DT;
+        // row nodes of tile (I, J) own slot J + 1, column nodes slot I
+        double* rowp = p.node_partial + ((size_t)tl * (nb + 1) + (J0 / AME_DT + 1)) * n * AME_NODE_SUMS;
+        double* colp = p.node_partial + ((size_t)tl * (nb + 1) + I0 / AME_DT) * n * AME_NODE_SUMS;
+        unsigned sel = 0u;   // bit 4 s + g: the lane's pair (s, g) is selected
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                if (ame_upper_pair(ld.i(g), ld.j(s), n) && predict_pair_selected(p, tl, ld.i(g), ld.j(s)))
+                    sel |= 1u << (4 * s + g);
+        // K slots from q0 on; f(rp, v) fills the pair's K values as the row node i
+        // takes them; SWAP: the column node j takes them with sent and received
+        // (k, k ^ 1) exchanged
+        auto pass = [&](auto kc, auto swap, int q0, auto&& f) {
+            constexpr int K = decltype(kc)::value;
+            constexpr bool SWAP = decltype(swap)::value;
+            double rs[4][K], cs[4][K];
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int k = 0; k < K; ++k) rs[a][k] = cs[a][k] = 0.0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    if (sel & (1u << (4 * s + g))) {
+                        const float2 y = *(const float2*)(ys + ((size_t)ld.i(g) * p.ny + ld.j(s)) * 2);
+                        const ResidPair rp(p, y, acc[0][s][g], acc[1][s][g], acc[2][s][g], acc[3][s][g],
+                                           acc[4][s][g]);
+                        double v[K];
+                        f(rp, v);
+#pragma unroll
+                        for (int k = 0; k < K; ++k) {
+                            rs[g][k] += v[k];
+                            cs[s][k] += v[SWAP ? (k ^ 1) : k];
+                        }
+                    }
+                }
+            }
+            // row node 16 w + 4 lq + g: across the 16 lanes li of its row
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    double x = rs[g][k];
+                    x += __shfl_xor(x, 1);
+                    x += __shfl_xor(x, 2);
+                    x += __shfl_xor(x, 4);
+                    x += __shfl_xor(x, 8);
+                    if (ld.li == 0 && ld.i(g) < n) rowp[(size_t)ld.i(g) * AME_NODE_SUMS + q0 + k] = x;
+                }
+            }
+            // column node 16 s + li: across the lane quarters lq, then the waves in order
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    double x = cs[s][k];
+                    x += __shfl_xor(x, 16);
+                    x += __shfl_xor(x, 32);
+                    if (ld.lq == 0) cl[ld.w][ld.col(s)][k] = x;
+                }
+            }
+            __syncthreads();
+            for (int e = threadIdx.x; e < AME_DT * K; e += AME_NT) {
+                const int cidx = e / K, k = e - cidx * K;
+                if (J0 + cidx < n)
+                    colp[(size_t)(J0 + cidx) * AME_NODE_SUMS + q0 + k] =
+                        ((cl[0][cidx][k] + cl[1][cidx][k]) + cl[2][cidx][k]) + cl[3][cidx][k];
+            }
+            __syncthreads();   // cl is free for the next pass
+        };
+        pass(std::integral_constant<int, 3>{}, std::false_type{}, 0, [&](const ResidPair& rp, double* v) {
+            v[0] = 1.0;
+            v[1] = -0.5 * (log(rp.det) + rp.m2 + LOG2PI2);
+            v[2] = rp.m2;
+        });
+        pass(std::integral_constant<int, 2>{}, std::true_type{}, 3, [&](const ResidPair& rp, double* v) {
+            v[0] = rp.q0 / rp.v0;
+            v[1] = rp.q1 / rp.v1;
+        });
+        pass(std::integral_constant<int, 4>{}, std::true_type{}, 5, [&](const ResidPair& rp, double* v) {
+            v[0] = rp.e0;
+            v[1] = rp.e1;
+            v[2] = rp.q0;
+            v[3] = rp.q1;
+        });
+        return;
+    }
+    if (MODE == 7) {   // histogram of m^2, one count per selected pair
+        __shared__ unsigned hl[AME_RANK_MAX_BINS];
+        const int nb = p.nbins;
+        for (int e = threadIdx.x; e < nb; e += AME_NT) hl[e] = 0u;
+        __syncthreads();
+        const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = ld.j(s);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = ld.i(g);
+                if (ame_upper_pair(i, j, n) && predict_pair_selected(p, tl, i, j)) {
+                    const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
+                    const ResidPair rp(p, y, acc[0][s][g], acc[1][s][g], acc[2][s][g], acc[3][s][g], acc[4][s][g]);
+                    atomicAdd(&hl[resid_bin(p, rp.m2)], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        unsigned long long* hs = p.hist + (size_t)tl * nb;
+        for (int e = threadIdx.x; e < nb; e += AME_NT) {
+            const unsigned v = hl[e];
+            if (v) atomicAdd(&hs[e], (unsigned long long)v);
+        }
+        return;
+    }
+    if (MODE == 8) {   // records of the pairs at or above the slice's threshold bin of m^2
+        __shared__ unsigned lcnt;
+        __shared__ unsigned long long gbase;
+        if (threadIdx.x == 0) lcnt = 0u;
+        __syncthreads();
+        const int bmin = p.bin_min[tl];
+        const float* ys = p.Yt + (size_t)tl * n * p.ny * 2;
+        unsigned take = 0u;   // bit 4 s + g of this lane's 16 pairs
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = ld.j(s);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = ld.i(g);
+                if (ame_upper_pair(i, j, n) && predict_pair_selected(p, tl, i, j)) {
+                    const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
+                    const ResidPair rp(p, y, acc[0][s][g], acc[1][s][g], acc[2][s][g], acc[3][s][g], acc[4][s][g]);
+                    if (resid_bin(p, rp.m2) >= bmin) take |= 1u << (4 * s + g);
+                }
+            }
+        }
+        const unsigned mine = __popc(take);
+        const unsigned lbase = mine ? atomicAdd(&lcnt, mine) : 0u;
+        __syncthreads();
+        if (threadIdx.x == 0 && lcnt) gbase = atomicAdd(&p.count[tl], (unsigned long long)lcnt);
+        __syncthreads();
+        if (!mine) return;
+        const long long off = p.offset[tl];
+        const long long cap = p.offset[tl + 1] - off;   // <= 0: nothing is written
+        long long pos = (long long)(gbase + lbase);
+        ame_resid_record* rs = p.rrec + off;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int j = ld.j(s);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i = ld.i(g);
+                if (take & (1u << (4 * s + g))) {
+                    if (pos < cap) {   // beyond the region: counted, not written
+                        const float2 y = *(const float2*)(ys + ((size_t)i * p.ny + j) * 2);
+                        const ResidPair rp(p, y, acc[0][s][g], acc[1][s][g], acc[2][s][g], acc[3][s][g],
+                                           acc[4][s][g]);
+                        ame_resid_record rc;
+                        rc.m2 = rp.m2;
+                        rc.z0 = rp.e0 / sqrt(rp.v0);
+                        rc.z1 = rp.e1 / sqrt(rp.v1);
+                        rc.slice = p.slice0 + tl;
+                        rc.i = i;
+                        rc.j = j;
+                        rc.pad = 0;
+                        rs[pos] = rc;
+                    }
+                    ++pos;
+                }
+            }
+        }
+        return;
+    }
     if (MODE == 0) {
         double sm[AME_PNS];
 #pragma unroll
@@ -543,6 +762,11 @@ long long ame_probit_score_work_doubles(const ame_dims* dm) {
 }
 // ame_probit_rank / ame_probit_select keep nothing per tile: the feature rows only
 long long ame_probit_rank_work_doubles(const ame_dims* dm) { return predict_feat_doubles(dm); }
+// ame_resid_nodes: the feature rows, then one [n][AME_NODE_SUMS] row per slice and slot
+long long ame_resid_nodes_work_doubles(const ame_dims* dm) {
+    const long long nb = (dm->n + AME_DT - 1) / AME_DT;
+    return predict_feat_doubles(dm) + (long long)dm->T_local * (nb + 1) * dm->n * AME_NODE_SUMS;
+}
 long long ame_mstep_dyad_blocks(const ame_dims* dm) {
     const long long a = (long long)dm->T_local * dm->n, b = (long long)dm->T_local * ame_tri_tiles(dm->n);
     return a > b ? a : b;
@@ -585,6 +809,8 @@ static PredictParams predict_common(const ame_dims* dm, const float* x, const fl
     p.offset = nullptr;
     p.count = nullptr;
     p.rec = nullptr;
+    p.node_partial = nullptr;
+    p.rrec = nullptr;
     return p;
 }
 
@@ -676,6 +902,89 @@ static int launch_probit_select(const ame_dims* dm, const ame_probit_select_args
     hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 5>), dim3((unsigned)((long long)S * p.ntile)),
                        dim3(AME_NT), 0, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+static void resid_noise(PredictParams& p, const double* noise) {
+    p.n00 = noise[0];
+    p.n01 = 0.5 * (noise[1] + noise[2]);
+    p.n11 = noise[3];
+}
+
+// MODE 6: per-node sums; the partial's slots are all written, then added in slot order
+template <int R>
+static int launch_resid_nodes(const ame_dims* dm, const ame_resid_nodes_args* a, hipStream_t st) {
+    const int S = dm->T_local, n = dm->n, nb = (n + AME_DT - 1) / AME_DT;
+    PredictParams p = predict_common<R>(dm, a->x, a->cov, a->Yt, a->Mt, a->mask_select, a->work, st);
+    resid_noise(p, a->noise);
+    p.node_partial = p.partial;
+    hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 6>), dim3((unsigned)((long long)S * p.ntile)),
+                       dim3(AME_NT), 0, st, p);
+    ame_col_sum(p.node_partial, nb + 1, n * AME_NODE_SUMS, 0, n * AME_NODE_SUMS, S, a->node, st);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// MODE 7: histogram of m^2; hist is zeroed on the stream first
+template <int R>
+static int launch_resid_hist(const ame_dims* dm, const ame_resid_hist_args* a, hipStream_t st) {
+    const int S = dm->T_local;
+    PredictParams p = predict_common<R>(dm, a->x, a->cov, a->Yt, a->Mt, a->mask_select, a->work, st);
+    resid_noise(p, a->noise);
+    p.nbins = a->nbins;
+    p.scale = a->scale;
+    p.hist = (unsigned long long*)a->hist;
+    if (hipMemsetAsync(a->hist, 0, (size_t)S * a->nbins * sizeof(uint64_t), st) != hipSuccess) return -3;
+    hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 7>), dim3((unsigned)((long long)S * p.ntile)),
+                       dim3(AME_NT), 0, st, p);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// MODE 8: records at or above bin_min; count is zeroed on the stream first
+template <int R>
+static int launch_resid_select(const ame_dims* dm, const ame_resid_select_args* a, hipStream_t st) {
+    const int S = dm->T_local;
+    PredictParams p = predict_common<R>(dm, a->x, a->cov, a->Yt, a->Mt, a->mask_select, a->work, st);
+    resid_noise(p, a->noise);
+    p.nbins = a->nbins;
+    p.scale = a->scale;
+    p.bin_min = a->bin_min;
+    p.slice0 = a->slice0;
+    p.offset = (const long long*)a->offset;
+    p.count = (unsigned long long*)a->count;
+    p.rrec = a->records;
+    if (hipMemsetAsync(a->count, 0, (size_t)S * sizeof(uint64_t), st) != hipSuccess) return -3;
+    hipLaunchKernelGGL((ame_predict_pairs_kernel<R, 8>), dim3((unsigned)((long long)S * p.ntile)),
+                       dim3(AME_NT), 0, st, p);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int AME_PFN(ame_resid_nodes_dispatch)(const ame_dims* dm, const ame_resid_nodes_args* a, hipStream_t st) {
+    switch (dm->r) {
+#define X(RR) \
+    case RR: return launch_resid_nodes<RR>(dm, a, st);
+        AME_FOR_EACH_R(X)
+#undef X
+        default: return -1;
+    }
+}
+
+int AME_PFN(ame_resid_hist_dispatch)(const ame_dims* dm, const ame_resid_hist_args* a, hipStream_t st) {
+    switch (dm->r) {
+#define X(RR) \
+    case RR: return launch_resid_hist<RR>(dm, a, st);
+        AME_FOR_EACH_R(X)
+#undef X
+        default: return -1;
+    }
+}
+
+int AME_PFN(ame_resid_select_dispatch)(const ame_dims* dm, const ame_resid_select_args* a, hipStream_t st) {
+    switch (dm->r) {
+#define X(RR) \
+    case RR: return launch_resid_select<RR>(dm, a, st);
+        AME_FOR_EACH_R(X)
+#undef X
+        default: return -1;
+    }
 }
 
 int AME_PFN(ame_probit_rank_dispatch)(const ame_dims* dm, const ame_probit_rank_args* a, hipStream_t st) {

@@ -658,6 +658,96 @@ class DeviceEngine:
                 _lib.check(self.L.ame_probit_select(ctypes.byref(dm), ctypes.byref(a), sp), "ame_probit_select")
         return rec, count
 
+    # ------------------------------------------------------------------
+    # residual diagnostics (ame_resid_nodes / ame_resid_hist / ame_resid_select)
+    # ------------------------------------------------------------------
+    def _resid_chunks(self, x, cov, work_size):
+        S = int(x.shape[0])
+        assert tuple(x.shape) == (S, self.n, self.d) and tuple(cov.shape) == (S, self.n, self.d, self.d)
+        assert x.is_contiguous() and cov.is_contiguous()
+        chunk, wk = self._slice_chunk(work_size, S)
+        return S, chunk, wk
+
+    def resid_nodes(self, x, cov, Yt, include_noise=True, Mt=None, mask_select=0):
+        """ame_resid_nodes over a stack of slices: the per-node sums
+        [S][n][AME_NODE_SUMS] (fp64, device) of the dyad scores of Yt.  Whole
+        slices at a time within the scratch budget of predict(); a slice's rows
+        do not depend on the split.  Runs on the ELBO stream; the caller has
+        dropped speculation."""
+        S, chunk, wk = self._resid_chunks(x, cov, self.L.ame_resid_nodes_work_size)
+        n = self.n
+        with torch.cuda.device(self.dev):
+            node = torch.empty(S, n, _lib.AME_NODE_SUMS, dtype=torch.float64, device=self.dev)
+        with self._elbo_call("resid_nodes") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_resid_nodes_args(
+                    x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]), Yt=_ptr(Yt[s0:s1]),
+                    noise=self.noise4(include_noise), node=_ptr(node[s0:s1]), work=_ptr(wk),
+                    work_doubles=wk.numel(), Mt=_ptr(Mt[s0:s1]) if Mt is not None else None,
+                    mask_select=int(mask_select))
+                _lib.check(self.L.ame_resid_nodes(ctypes.byref(dm), ctypes.byref(a), sp), "ame_resid_nodes")
+        return node
+
+    def resid_hist(self, x, cov, Yt, nbins, m2_max, include_noise=True, Mt=None, mask_select=0):
+        """ame_resid_hist over a stack of slices: the histograms [S][nbins]
+        (int64, device) of the pairs' m^2.  Chunked like resid_nodes; integer
+        counts, so a slice's row does not depend on the split."""
+        from . import residuals
+        nbins, m2_max = residuals.check_bins(nbins, m2_max)
+        S, chunk, wk = self._resid_chunks(x, cov, self.L.ame_resid_hist_work_size)
+        n = self.n
+        with torch.cuda.device(self.dev):
+            hist = torch.empty(S, nbins, dtype=torch.int64, device=self.dev)
+        with self._elbo_call("resid_hist") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_resid_hist_args(
+                    x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]), Yt=_ptr(Yt[s0:s1]),
+                    noise=self.noise4(include_noise), hist=_ptr(hist[s0:s1]), work=_ptr(wk),
+                    work_doubles=wk.numel(), Mt=_ptr(Mt[s0:s1]) if Mt is not None else None,
+                    mask_select=int(mask_select), nbins=nbins, scale=residuals.scale(nbins, m2_max))
+                _lib.check(self.L.ame_resid_hist(ctypes.byref(dm), ctypes.byref(a), sp), "ame_resid_hist")
+        return hist
+
+    def resid_select(self, x, cov, Yt, nbins, m2_max, bin_min, offset, include_noise=True, Mt=None,
+                     mask_select=0):
+        """ame_resid_select over a stack of slices: every selected pair whose bin
+        of m^2 is at least bin_min[s] as a record in slice s's region
+        [offset[s], offset[s + 1]).  bin_min (S,) and offset (S + 1,) are host
+        integers.  Returns (records: int64 words on the device, 5 per record,
+        residuals.RECORD; count (S,) int64: the pairs that passed, which exceeds
+        a region's size where some were dropped).  Chunked like resid_hist."""
+        from . import residuals
+        nbins, m2_max = residuals.check_bins(nbins, m2_max)
+        S, chunk, wk = self._resid_chunks(x, cov, self.L.ame_resid_select_work_size)
+        n = self.n
+        off = torch.as_tensor(offset, dtype=torch.int64).reshape(-1)
+        bmin = torch.as_tensor(bin_min, dtype=torch.int32).reshape(-1)
+        if off.numel() != S + 1 or bmin.numel() != S or int(off[0]) < 0 or bool((off[1:] < off[:-1]).any()):
+            raise ValueError("resid_select: offset must hold S + 1 non-decreasing record offsets from >= 0 "
+                             "and bin_min S bins")
+        with torch.cuda.device(self.dev):
+            rec = torch.zeros(max(1, int(off[-1])) * (residuals.RECORD.itemsize // 8), dtype=torch.int64,
+                              device=self.dev)
+            count = torch.empty(S, dtype=torch.int64, device=self.dev)
+            d_off, d_bmin = off.to(self.dev), bmin.to(self.dev)
+        with self._elbo_call("resid_select") as sp:
+            for s0 in range(0, S, chunk):
+                s1 = min(S, s0 + chunk)
+                dm = _lib.ame_dims(n, self.r, s1 - s0, 0, s1 - s0, self.vcode)
+                a = _lib.ame_resid_select_args(
+                    x=_ptr(x[s0:s1]), cov=_ptr(cov[s0:s1]), Yt=_ptr(Yt[s0:s1]),
+                    noise=self.noise4(include_noise), work=_ptr(wk), work_doubles=wk.numel(),
+                    Mt=_ptr(Mt[s0:s1]) if Mt is not None else None, mask_select=int(mask_select),
+                    nbins=nbins, scale=residuals.scale(nbins, m2_max), bin_min=_ptr(d_bmin[s0:s1]),
+                    slice0=s0, reserved=0, offset=_ptr(d_off[s0:s1 + 1]), count=_ptr(count[s0:s1]),
+                    records=_ptr(rec))
+                _lib.check(self.L.ame_resid_select(ctypes.byref(dm), ctypes.byref(a), sp), "ame_resid_select")
+        return rec, count
+
     def mask_args(self, select):
         """(Yt, Mt, mask_select) for predict / mstep_stats: the packed observations
         (never the working network) with the mask and a selector, or the

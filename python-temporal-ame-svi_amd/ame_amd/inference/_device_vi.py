@@ -646,6 +646,141 @@ class DeviceTemporalVI(BaseTemporalVariationalInference):
                               mask_select=select)
         return self._check_dict(sums, levels)
 
+    # ---------------- residual diagnostics of a Gaussian fit (extension) ----------------
+    # predictive_check reduces a fit to sums per time step; these calls keep the
+    # node and the pair: per-node sums of the dyad scores, the distribution of the
+    # Mahalanobis distance m2 = e' Sigma^-1 e and the k most surprising pairs, all
+    # formed tile by tile on the device (ame_resid_nodes / ame_resid_hist /
+    # ame_resid_select); no dyad moment is moved to the host.  The host finish is
+    # ame_amd/residuals.py.
+    def _resid_refuse(self, what):
+        self._refuse_binary(what, "it scores Gaussian observations; link_roc and top_links rank the "
+                            "links of a binary model")
+        if self._time_sharded():
+            raise NotImplementedError(f"{what} is not available on a time-sharded run: fit on one process")
+
+    def _resid_state(self, what, subset, smoothed):
+        """(engine, means, covariances, Yt, Mt, mask_select) of the in-sample calls,
+        chosen as predictive_check chooses them."""
+        self._resid_refuse(what)
+        select = self._subset(subset)
+        eng, x, cov, _ = self._state(smoothed)
+        Yt, Mt, select = eng.mask_args(select)
+        return eng, x, cov, Yt, Mt, select
+
+    @staticmethod
+    def _check_k(k, least=1):
+        if isinstance(k, bool) or int(k) != k or int(k) < least:
+            raise ValueError(f"k must be an integer >= {least} (got {k!r})")
+        return int(k)
+
+    @staticmethod
+    def _top_residuals(eng, x, cov, Yt, Mt, select, hist, k, bins, m2_max, include_noise, max_records):
+        """top_residuals' fields for a stack of slices whose histograms are `hist`."""
+        import numpy as np
+        from .. import residuals
+        bin_min, capacity = residuals.threshold(hist, k)
+        total = int(capacity.sum())
+        if total > int(max_records):
+            raise ValueError(f"{total} candidate records exceed max_records={int(max_records)}: too many pairs "
+                             f"share the threshold bin (they saturate the open last bin beyond m2_max={m2_max}, "
+                             f"or bins={bins} is too coarse); raise m2_max or bins, or ask for fewer slices")
+        offset = np.concatenate([[0], np.cumsum(capacity)]).astype(np.int64)
+        rec, count = eng.resid_select(x, cov, Yt, bins, m2_max, bin_min, offset, include_noise=include_noise,
+                                      Mt=Mt, mask_select=select)
+        count = count.to("cpu").numpy()
+        if not np.array_equal(count, capacity):   # the two passes bin the same m2: cannot differ
+            raise RuntimeError(f"ame_resid_select passed {count.tolist()} pairs, the histograms "
+                               f"promise {capacity.tolist()}")
+        records = rec.to("cpu").numpy().view(residuals.RECORD)[:total]
+        return residuals.top_k(records, offset, k)
+
+    def node_check(self, include_noise=True, smoothed=False, subset=None) -> dict:
+        """:meth:`predictive_check` per node: for every time step and node the
+        sums over the chosen pairs that contain it.  ``pairs`` (T, n) int64;
+        ``log_score`` and ``mahalanobis`` (T, n), the pair's log N(y; E mu,
+        Sigma) and m2; ``z2``, ``resid`` (the signed bias) and ``sq_err``
+        (T, n, 2), last axis [the entries the node sends, the entries it
+        receives]; ``mean_mahalanobis`` = mahalanobis / pairs (2 under the
+        model; NaN where pairs == 0).  ``include_noise``, ``smoothed`` and
+        ``subset`` as in :meth:`predictive_check`; with covariates the residual
+        network the fit reads is scored.  Summed over the nodes every field is
+        twice predictive_check's.  Not available on a binary model or a
+        time-sharded run.  Does not modify this object."""
+        from .. import residuals
+        eng, x, cov, Yt, Mt, select = self._resid_state("node_check", subset, smoothed)
+        node = eng.resid_nodes(x, cov, Yt, include_noise=include_noise, Mt=Mt, mask_select=select)
+        return residuals.node_dict(node.to("cpu").numpy())
+
+    def residual_histogram(self, bins=1024, m2_max=64.0, subset=None, smoothed=False,
+                           include_noise=True) -> dict:
+        """The distribution of the pairs' Mahalanobis distance m2 per time step:
+        ``edges`` (bins + 1,), ``hist`` (T, bins) int64, ``expected`` (T, bins)
+        fp64, the counts of a chi-square with 2 degrees of freedom (what a
+        calibrated fit gives), and ``pairs`` (T,).  ``bins`` (1 .. 2048) equal
+        bins cover [0, m2_max); the last one also holds what lies beyond and any
+        NaN.  The other arguments as in :meth:`node_check`."""
+        from .. import residuals
+        bins, m2_max = residuals.check_bins(bins, m2_max)
+        eng, x, cov, Yt, Mt, select = self._resid_state("residual_histogram", subset, smoothed)
+        hist = eng.resid_hist(x, cov, Yt, bins, m2_max, include_noise=include_noise, Mt=Mt, mask_select=select)
+        return residuals.histogram(hist.to("cpu").numpy(), bins, m2_max)
+
+    def top_residuals(self, k=100, bins=1024, m2_max=64.0, subset=None, smoothed=False, include_noise=True,
+                      max_records=2 ** 24) -> dict:
+        """The k most surprising pairs of every time step, most surprising first
+        by (NaN first, -m2, i, j): ``i``, ``j`` (T, k) int64 with i < j, ``m2``
+        and ``p_value`` = exp(-m2 / 2) (T, k), ``z`` (T, k, 2) the signed
+        standardised residuals of the entries i -> j and j -> i; a step with
+        fewer than k pairs is padded with -1 / NaN.  The device keeps the pairs
+        at or above the histogram bin that holds the k-th m2; more than
+        ``max_records`` of them is a ValueError (many pairs lie beyond
+        ``m2_max``: raise ``m2_max`` or ``bins``).  The other arguments as in
+        :meth:`node_check`."""
+        from .. import residuals
+        bins, m2_max = residuals.check_bins(bins, m2_max)
+        k = self._check_k(k)
+        eng, x, cov, Yt, Mt, select = self._resid_state("top_residuals", subset, smoothed)
+        hist = eng.resid_hist(x, cov, Yt, bins, m2_max, include_noise=include_noise, Mt=Mt, mask_select=select)
+        return self._top_residuals(eng, x, cov, Yt, Mt, select, hist.to("cpu").numpy(), k, bins, m2_max,
+                                   include_noise, max_records)
+
+    def forecast_residuals(self, Y_future, k=100, W_future=None, missing_future=None, bins=1024, m2_max=64.0,
+                           smoothed=False, include_noise=True, max_records=2 ** 24) -> dict:
+        """:meth:`node_check`, :meth:`residual_histogram` and :meth:`top_residuals`
+        of held-out steps: ``Y_future`` (n, n, h, 2) against the h-step forecast,
+        packed and (``W_future``, ``missing_future``) prepared as
+        :meth:`forecast_check` does.  Returns ``{"nodes": ..., "histogram": ...,
+        "top": ...}`` with h rows each; ``top`` is None when k == 0."""
+        from .. import residuals
+        bins, m2_max = residuals.check_bins(bins, m2_max)
+        k = self._check_k(k, least=0)
+        self._resid_refuse("forecast_residuals")
+        Y_future = torch.as_tensor(Y_future)
+        if Y_future.dim() != 4 or tuple(Y_future.shape[:2]) != (self.n, self.n) or Y_future.shape[3] != 2 \
+                or Y_future.shape[2] < 1:
+            raise ValueError(f"Y_future has shape {tuple(Y_future.shape)}, expected ({self.n}, {self.n}, h, 2)")
+        Wf = self._future_covariates(W_future, Y_future.shape[2] if Y_future.dim() == 4 else 1)
+        if Wf is not None:
+            Y_future = Y_future.to("cpu", torch.float32) - self.model.covariate_effect(Wf)
+        eng, (m, S) = self._forecast_states(int(Y_future.shape[2]) if Y_future.dim() == 4 else 1, smoothed)
+        Yt = eng.pack_future(Y_future)
+        Mt, select = None, 0
+        if missing_future is not None:
+            mf = torch.as_tensor(missing_future)
+            if mf.dim() != 3 or int(mf.shape[2]) != int(Yt.shape[0]):
+                raise ValueError(f"missing_future has shape {tuple(mf.shape)}, expected "
+                                 f"({self.n}, {self.n}, {int(Yt.shape[0])})")
+            Mt, _, _ = eng.pack_mask(mf, "missing_future")
+            select = self._SUBSETS["observed"]
+        kw = dict(include_noise=include_noise, Mt=Mt, mask_select=select)
+        node = eng.resid_nodes(m, S, Yt, **kw)
+        hist = eng.resid_hist(m, S, Yt, bins, m2_max, **kw).to("cpu").numpy()
+        top = self._top_residuals(eng, m, S, Yt, Mt, select, hist, k, bins, m2_max, include_noise,
+                                  max_records) if k else None
+        return {"nodes": residuals.node_dict(node.to("cpu").numpy()),
+                "histogram": residuals.histogram(hist, bins, m2_max), "top": top}
+
     def forecast_dyads(self, n_steps: int = 1, rows=None, cols=None, include_noise=True,
                        max_elements=2 ** 27, smoothed=False, W_future=None):
         """predict_dyads of the h-step forecast: (ni, nj, h, 2) and (ni, nj, h, 3).
